@@ -19,7 +19,18 @@ Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line o
 torchrun (WORLD_SIZE set) this process is one rank and `--gpus` must equal WORLD_SIZE; started
 plainly with N > 1 it launches the N ranks itself, or exits non-zero when fewer than N GPUs are
 visible (image_recommender_amd/launch.py).  `value` = Q*K / max-over-ranks wall time of the K
-steps, inputs resident in HBM.
+steps, inputs resident in HBM; `ms_per_step` = that wall time / K.
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps,
+the result line.  `--full` adds every other leg to the same line: the rocprofv3 counter passes,
+the candidate-kernel duration (a second region of K steps with HIP events) and the roofline
+figures, the per-rank phase times, recall@k against the float64 ground truth, the single-query
+regime (warm and cold) and the CPU comparator.  `--profile-only` is the diagnostic form for
+profiler runs and A/B scripts: the timed steps, the kernel-event region and the phase region, its
+own short JSON line.  `--dump-outputs DIR` writes the (Q, k) distances and labels the last timed
+step returned as DIR/distances.npy (float32) and DIR/labels.npy (float64: row ids are < 2^53);
+queries and corpus are seeded by the arguments alone, so two builds can be compared output for
+output.
 """
 from __future__ import annotations
 
@@ -40,6 +51,7 @@ MFMA_F32_PEAK_TFLOPS = 157.3     # MI355X dense fp32 matrix peak (MI355X_MICROAR
 MFMA_BF16_PEAK_TFLOPS = 2516.8   # dense bf16 MFMA peak = 16 x the f32 rate (MI355X_MICROARCH.md)
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E peak (spec)
 BLOCK = 16384                    # rows per generation block (the seed unit)
+DUMP_MAX_BYTES = 64 * 10**6      # --dump-outputs writes at most this much in all
 
 CONFIGS = {
     2: dict(name="cfg2: 1M x 768 DreamSim-only, L2", rows=1_000_000, parts=(768,), centres=(1000,),
@@ -64,19 +76,29 @@ def parse():
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--query-groups", type=int, default=1,
                     help="query slices of the N ranks (sharded.py query x row partition)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: rocprofv3 counter "
+                         "passes, kernel duration + roofline, phase times, recall@k vs float64, the "
+                         "single-query regime and the CPU comparator (the options below that name "
+                         "--full shape those legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's distances / labels to "
+                         "DIR/distances.npy (float32) and DIR/labels.npy (float64)")
     ap.add_argument("--gt-queries", type=int, default=1024,
-                    help="queries checked for recall@k (default: the whole batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget")
-    ap.add_argument("--single-query-steps", type=int, default=50)
+                    help="--full: queries checked for recall@k (default: the whole batch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU comparator")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget")
+    ap.add_argument("--single-query-steps", type=int, default=50, help="--full: single-query steps")
     ap.add_argument("--mode", choices=("auto", "exact", "split", "bf16", "i8"), default="auto",
                     help="search arithmetic (include/imgrec_knn.h knn_search_mode)")
     ap.add_argument("--profile-only", action="store_true",
-                    help="only the timed steps (for rocprofv3 runs)")
+                    help="only the timed steps, the kernel-event region and the phase region (for "
+                         "rocprofv3 runs)")
     ap.add_argument("--no-phases", action="store_true",
-                    help="skip the per-rank phase region (its event records show in kernel traces)")
+                    help="--full / --profile-only: skip the per-rank phase region (its event "
+                         "records show in kernel traces)")
     ap.add_argument("--pmc", choices=("auto", "off"), default="auto",
-                    help="auto: at N = 1 on configs 2 / 3, measure the dominant kernel's HBM traffic, "
+                    help="--full; auto: at N = 1 on configs 2 / 3, measure the dominant kernel's HBM traffic, "
                          "clock and MFMA busy in rocprofv3 --pmc passes of this same workload "
                          "before the timed run (the committed profiles/ records otherwise)")
     return ap.parse_args()
@@ -397,12 +419,27 @@ def live_pmc(a, budget_s: float = 150.0):
     return res, f"{len(PMC_PASSES)} rocprofv3 --pmc passes of this workload, {time.perf_counter() - t0:.0f} s"
 
 
+def dump_outputs(dirname: str, Dr, Ir):
+    """--dump-outputs: what the last timed step returned to its caller, (Q, k) squared distances
+    and global row labels, as float32 / float64 arrays (40 + 80 KB at the default Q and k).  Beyond
+    DUMP_MAX_BYTES in all, a fixed seeded sample of the query rows (their indices in rows.npy)."""
+    os.makedirs(dirname, exist_ok=True)
+    D, I = Dr.detach().cpu().numpy(), Ir.detach().cpu().numpy()
+    keep = DUMP_MAX_BYTES // (12 * max(D.shape[1], 1) + 8)
+    if D.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(0).choice(D.shape[0], size=keep, replace=False))
+        D, I = D[rows], I[rows]
+        np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "distances.npy"), D.astype(np.float32))
+    np.save(os.path.join(dirname, "labels.npy"), I.astype(np.float64))
+
+
 def main():
     a = parse()
     live = None
     # (not under a profiler already: rocprofv3 exports ROCPROF_* to the program it runs)
     profiled = any(k.startswith("ROCPROF") for k in os.environ)
-    if (a.pmc == "auto" and a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.profile_only
+    if (a.full and a.pmc == "auto" and a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.profile_only
             and a.config in (2, 3) and not profiled):
         try:
             live = live_pmc(a)
@@ -544,8 +581,11 @@ def main():
     elapsed, _, (Dr, Ir) = region(step, a.steps, False)          # the bench value
     split_q, fallback_q, err_ratio = shard.index.search_stats(with_error=True)   # last step
     path = lib.knn_last_path(h)                                # 0 exact, 1 split, 2 bf16, 3 i8
-    kel, kern_ms, _ = region(step, a.steps, True)               # candidate-kernel duration
-    per_rank = None if a.no_phases else phases(a.steps)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, Dr, Ir)
+    extras = a.full or a.profile_only        # a plain run stops at the timed steps
+    kel, kern_ms, _ = region(step, a.steps, True) if extras else (None, None, None)   # candidate-kernel duration
+    per_rank = phases(a.steps) if extras and not a.no_phases else None
     if a.profile_only:
         if rank == 0:
             print(json.dumps({"elapsed_s": elapsed, "ms_per_step": elapsed / a.steps * 1e3,
@@ -553,6 +593,50 @@ def main():
                               "kernel_ms": kern_ms, "split_queries": split_q,
                               "fallback_queries": fallback_q, "err_ratio": err_ratio,
                               "world_size": world, "per_rank": per_rank}))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    tr, tq, sp, wg = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    lib.knn_plan(shard.index.handle, nq_local, a.k, C.byref(tr), C.byref(tq), C.byref(sp), C.byref(wg))
+    n_local = shard.local_rows
+    split = split_q > 0
+    dtype = {2: "bf16 candidates (fp32 accumulate) + fp32 rerank, certified exact",
+             1: "bf16x3 split (fp32-equivalent) + fp32 rerank"}.get(path, "fp32")
+    # the headline line: everything a plain run reports (--full appends its legs to it below)
+    out = {
+        "metric": "k-NN queries/sec + recall@10 on 1M concat vectors at 1/2/4/8 MI355X",
+        "value": a.nq * a.steps / elapsed,
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": dtype,
+        "search_mode": a.mode,
+        "search_path": {0: "exact", 1: "split", 2: "bf16"}.get(path, "?"),
+        "candidate_path": {"queries": split_q, "certificate_fallbacks": fallback_q,
+                           "max_err_over_bound": err_ratio} if split else None,
+        "data": "synthetic, generated on device (Gaussian-mixture parts, per-part L2-normalised)",
+        "config": {
+            "workload": cfg["name"], "rows": cfg["rows"], "dim": D_total, "k": a.k,
+            "queries_per_batch": a.nq, "metric": cfg["ranking"],
+            "rows_per_gpu": n_local, "parallelism": (f"query-slice x{qgroups} * row-shard x{world // qgroups}" if qgroups > 1
+                            else f"row-shard x{world}") + (" + RCCL all-gather merge" if backend == "nccl"
+                                                           else f" + {backend} all-gather merge (rehearsal)"),
+            "queries_per_gpu": nq_local,
+            "tile_rows": tr.value, "tile_queries": tq.value, "row_splits": sp.value,
+            "workgroups": wg.value,
+        },
+        "build_s": build_s,
+        "world_size": dist.get_world_size() if world > 1 else 1,
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out))
         if world > 1:
             dist.destroy_process_group()
         return
@@ -596,17 +680,12 @@ def main():
     del other
     path1 = lib.knn_last_path(h)                               # 0 exact, 1 split, 2 bf16, 3 i8
 
-    tr, tq, sp, wg = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    lib.knn_plan(shard.index.handle, nq_local, a.k, C.byref(tr), C.byref(tq), C.byref(sp), C.byref(wg))
-
     cpu = None
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(torch, cfg, centres, {"rows": cfg["rows"]}, a.k, seed, a.cpu_seconds, a.nq)
 
     if rank == 0:
-        n_local = shard.local_rows
         flops = 2.0 * n_local * D_total * nq_local
-        split = split_q > 0
         kbuf = C.create_string_buffer(128)
         lib.knn_plan_kernel(shard.index.handle, nq_local, a.k, kbuf, 128)
         kname, kpat = kernel_pattern(tr.value, tq.value, path, a.k, kbuf.value.decode())
@@ -631,8 +710,6 @@ def main():
         peak_basis = {2: "bf16 dense MFMA 2516.8 TF/s (one MFMA per product)",
                       1: "bf16 dense MFMA 2516.8 TF/s / 3 MFMAs per product"}.get(
                           path, "fp32 dense MFMA (v_mfma_f32_32x32x2_f32)")
-        dtype = {2: "bf16 candidates (fp32 accumulate) + fp32 rerank, certified exact",
-                 1: "bf16x3 split (fp32-equivalent) + fp32 rerank"}.get(path, "fp32")
         bytes1 = 4.0 * n_local * D_total + 4.0 * n_local    # the fp32 corpus + norms (algorithmic)
         dpb = (D_total + 63) // 64 * 64
         # what the single-query kernel actually streams: the int8 copy (codes + one fp32 scale per
@@ -640,34 +717,7 @@ def main():
         # the fp32 rows
         stream1 = ({3: 1.0 * n_local * dpb + 4.0 * n_local * (dpb // 64), 2: 2.0 * n_local * dpb}
                    .get(path1, 4.0 * n_local * D_total) + 4.0 * n_local)
-        qps = a.nq * a.steps / elapsed
-        out = {
-            "metric": "k-NN queries/sec + recall@10 on 1M concat vectors at 1/2/4/8 MI355X",
-            "value": qps,
-            "unit": "queries/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": dtype,
-            "search_mode": a.mode,
-            "search_path": {0: "exact", 1: "split", 2: "bf16"}.get(path, "?"),
-            "candidate_path": {"queries": split_q, "certificate_fallbacks": fallback_q,
-                               "max_err_over_bound": err_ratio} if split else None,
-            "data": "synthetic, generated on device (Gaussian-mixture parts, per-part L2-normalised)",
-            "config": {
-                "workload": cfg["name"], "rows": cfg["rows"], "dim": D_total, "k": a.k,
-                "queries_per_batch": a.nq, "metric": cfg["ranking"],
-                "rows_per_gpu": n_local, "parallelism": (f"query-slice x{qgroups} * row-shard x{world // qgroups}" if qgroups > 1
-                                else f"row-shard x{world}") + (" + RCCL all-gather merge" if backend == "nccl"
-                                                               else f" + {backend} all-gather merge (rehearsal)"),
-                "queries_per_gpu": nq_local,
-                "tile_rows": tr.value, "tile_queries": tq.value, "row_splits": sp.value,
-                "workgroups": wg.value,
-            },
+        out.update({
             "recall_at_10": recall,
             "recall_queries": ngt,
             "labels_equal_fp64_frac": label_eq,
@@ -706,11 +756,9 @@ def main():
                 "fp32_equivalent_gbs": bytes1 / (kern1_ms * 1e-3) / 1e9,
                 "cpu_baseline": cpu["single_query"] if cpu else None,
             },
-            "build_s": build_s,
-            "world_size": dist.get_world_size() if world > 1 else 1,
             "per_rank": per_rank,
             "cpu_baseline": cpu,
-        }
+        })
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

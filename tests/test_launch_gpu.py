@@ -25,7 +25,7 @@ def _run(args, backend, timeout=400):
 
 def test_bench_two_ranks_without_torchrun():
     r = _run(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "200000",
-              "--no-cpu-baseline", "--single-query-steps", "2", "--pmc", "off", "--no-phases"], "gloo")
+              "--full", "--no-cpu-baseline", "--single-query-steps", "2", "--pmc", "off", "--no-phases"], "gloo")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1, r.stdout                      # rank 0's line only

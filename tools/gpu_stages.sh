@@ -5,8 +5,8 @@
 # stages:
 #   tests[=FILES]   pytest -m gpu (all, or the listed test files, comma-separated)
 #   smoke           __graft_entry__.smoke()
-#   bench           bench.py (default workload, CPU baseline included) -> bench.json
-#   bench2          bench.py --config 2 (1M x 768) -> bench_cfg2.json
+#   bench           bench.py --full (default workload, CPU baseline included) -> bench.json
+#   bench2          bench.py --full --config 2 (1M x 768) -> bench_cfg2.json
 #   rows125k        bench.py --rows 125000 --profile-only (the N = 8 per-rank step) -> rows125k.json
 #   nq1             bench.py --nq 1 --profile-only, cfg3 and cfg2 -> nq1_cfg{3,2}.json
 #   rocprof         rocprofv3 --kernel-trace --stats of a bench run -> prof/
@@ -48,10 +48,10 @@ for st in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || fail smoke $OUT/smoke.log
       tail -2 $OUT/smoke.log ;;
     bench)
-      timeout -k 10 500 python bench.py $BA > $OUT/bench.json 2> $OUT/bench.err || fail bench $OUT/bench.err
+      timeout -k 10 500 python bench.py --full $BA > $OUT/bench.json 2> $OUT/bench.err || fail bench $OUT/bench.err
       cat $OUT/bench.json ;;
     bench2)
-      timeout -k 10 500 python bench.py --config 2 --no-cpu-baseline $BA > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err || fail bench2 $OUT/bench_cfg2.err
+      timeout -k 10 500 python bench.py --full --config 2 --no-cpu-baseline $BA > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err || fail bench2 $OUT/bench_cfg2.err
       cat $OUT/bench_cfg2.json ;;
     rows125k)
       timeout -k 10 300 python bench.py --rows 125000 --profile-only --steps 200 --warmup 50 $BA > $OUT/rows125k.json 2> $OUT/rows125k.err || fail rows125k $OUT/rows125k.err
@@ -62,12 +62,12 @@ for st in "$@"; do
         cat $OUT/nq1_cfg$c.json
       done ;;
     rocprof)
-      timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline $BA > $OUT/prof.log 2>&1 || fail rocprof $OUT/prof.log
+      timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline $BA > $OUT/prof.log 2>&1 || fail rocprof $OUT/prof.log
       head -8 $OUT/prof/run_kernel_stats.csv | cut -c1-220 ;;
     rehearse)
       n=${arg:-8}
       IMGREC_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus $n --steps 3 --warmup 1 --single-query-steps 3 $BA \
+        --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus $n --steps 3 --warmup 1 --single-query-steps 3 $BA \
         > $OUT/rehearse_n$n.json 2> $OUT/rehearse_n$n.err || fail rehearse $OUT/rehearse_n$n.err
       cat $OUT/rehearse_n$n.json ;;
     rehearse_pipe)

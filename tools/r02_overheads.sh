@@ -6,7 +6,7 @@ set -u
 export PYTHONPATH=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/${1:-r02_over}; mkdir -p $OUT
-timeout -k 10 300 python bench.py --config 2 --no-cpu-baseline > $OUT/cfg2.json 2> $OUT/cfg2.err || { tail $OUT/cfg2.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config 2 --no-cpu-baseline > $OUT/cfg2.json 2> $OUT/cfg2.err || { tail $OUT/cfg2.err; exit 1; }
 cat $OUT/cfg2.json
 for R in 125000 1000000; do
   timeout -k 10 300 python bench.py --rows $R --profile-only --steps 50 --warmup 5 > $OUT/rows_$R.json 2>> $OUT/err.log || exit 2

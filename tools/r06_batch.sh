@@ -15,7 +15,7 @@ step epi
 bash tools/b16w_epi_split.sh $O/epi_cfg2 --config 2 || exit 2
 bash tools/b16w_epi_split.sh $O/epi_cfg3 --config 3 || exit 3
 step bench
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 4; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 4; }
 python -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['roofline']['frac'], d['roofline']['traffic'], d['roofline']['pmc_live'], d['single_query'])"
 step pipeline
 IMGREC_DIST_BACKEND=gloo timeout -k 10 600 python bench_pipeline.py --gpus 2 --images 8192 --model-batch 256 \

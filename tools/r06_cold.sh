@@ -10,5 +10,5 @@ done
 cat $O/nq1_cold.jsonl
 timeout -k 10 600 python -u -m pytest tests/test_launch_gpu.py -x -v --timeout 400 --timeout-method thread > $O/launch_tests.log 2>&1 || { tail -30 $O/launch_tests.log; exit 2; }
 tail -1 $O/launch_tests.log
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
 python3 -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['roofline']['frac'], d['single_query'])"

@@ -10,10 +10,10 @@ O=gpurun_out/${1:-r06/final}; mkdir -p $O
 [ -n "${SKIP_TESTS:-}" ] || tail -1 $O/gpu_tests.log
 [ -n "${SKIP_TESTS:-}" ] || timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $O/smoke.log; exit 2; }
 [ -n "${SKIP_TESTS:-}" ] || tail -1 $O/smoke.log
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 3; }
-timeout -k 10 600 python bench.py --config 2 > $O/bench_cfg2.json 2> $O/bench_cfg2.err || { echo "cfg2 bench failed"; tail -20 $O/bench_cfg2.err; exit 4; }
-timeout -k 10 300 python bench.py --rows 125000 --no-cpu-baseline --pmc off > $O/rows125k.json 2> $O/rows125k.err || { echo "125k failed"; exit 5; }
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --pmc off > $O/prof.log 2>&1 || { echo "rocprof failed"; tail -5 $O/prof.log; exit 6; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 3; }
+timeout -k 10 600 python bench.py --full --config 2 > $O/bench_cfg2.json 2> $O/bench_cfg2.err || { echo "cfg2 bench failed"; tail -20 $O/bench_cfg2.err; exit 4; }
+timeout -k 10 300 python bench.py --full --rows 125000 --no-cpu-baseline --pmc off > $O/rows125k.json 2> $O/rows125k.err || { echo "125k failed"; exit 5; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --pmc off > $O/prof.log 2>&1 || { echo "rocprof failed"; tail -5 $O/prof.log; exit 6; }
 find $O/prof -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_bench_under_rocprof.csv \;
 python3 - $O <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ done
 cat $O/hash.txt
 for r in 1 2; do
   for v in libimgrec.so libimgrec_rrnt.so; do
-    IMGREC_LIB_NAME=$v timeout -k 10 300 python bench.py --no-cpu-baseline --pmc off --single-query-steps 200 > $O/cfg3_${v}_$r.json 2>> $O/err.txt || exit 2
+    IMGREC_LIB_NAME=$v timeout -k 10 300 python bench.py --full --no-cpu-baseline --pmc off --single-query-steps 200 > $O/cfg3_${v}_$r.json 2>> $O/err.txt || exit 2
     IMGREC_LIB_NAME=$v timeout -k 10 300 python bench.py --rows 125000 --steps 200 --warmup 20 --profile-only --no-phases > $O/r125k_${v}_$r.json 2>> $O/err.txt || exit 3
     python3 -c "
 import json; a=json.load(open('$O/cfg3_${v}_$r.json')); b=json.load(open('$O/r125k_${v}_$r.json'))

@@ -8,6 +8,6 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 N=${1:-2}; shift
 OUT=gpurun_out/rehearse; mkdir -p $OUT
 IMGREC_DIST_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus $N --steps 3 --warmup 1 --single-query-steps 3 "$@" \
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus $N --steps 3 --warmup 1 --single-query-steps 3 "$@" \
   > $OUT/n$N.json 2> $OUT/n$N.err || { tail -30 $OUT/n$N.err; exit 1; }
 cat $OUT/n$N.json

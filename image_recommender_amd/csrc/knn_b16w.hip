@@ -61,7 +61,12 @@ constexpr int kLPW = (kBM + kBQ) / kRPP / kNW;   // DMA pieces per wave per stag
 constexpr int kNormSlots = 4;             // row-norm ring (tiles)
 constexpr int kNormOff = kNS * kStage;
 constexpr int kParkOff = kNormOff + kNormSlots * kBM * 4;   // per wave: 8 accumulators per lane
-constexpr int kLDS = kParkOff + kNW * 64 * 8 * 4;
+// shared screen bound: a wave's kQW query records (kSBWords words each: 2 KiB, by LDS-DMA) take
+// the park's place, and per query (lu, last published value) follows
+constexpr int kRecOff = kParkOff;
+constexpr int kLuOff = kParkOff + kNW * 64 * 8 * 4;
+constexpr int kLDS = kLuOff + kBQ * 2 * 4;
+static_assert(kQW * kSBWords * 4 == 64 * 8 * 4 && kSBWords == 16, "a wave's records fill its park area");
 constexpr int kQuads = 8;                 // MFMA quads per stage (2 k-steps x 4)
 // the query-tile waves issue their DMA after this quad of the next stage (the corpus-tile waves
 // issue theirs right after the barrier), so each SIMD's other wave feeds the MFMA pipe meanwhile
@@ -78,9 +83,7 @@ static_assert(kDeferQ >= 0 && kDeferQ < kQuads - 1, "deferred DMA inside the sta
 // v_cndmask tree instead of a ds_write / ds_read round trip per row (the norms stay in the
 // registers the screen loaded them into).  Bit-identical; cfg2 0.3-1.2 % faster, cfg3 the same
 // (profiles/r06/nopark/).
-#ifndef IMGREC_B16W_NOPARK
-#define IMGREC_B16W_NOPARK 1
-#endif
+// (the default, 1, is set in knn_kernels.h: the shared screen bound needs the park's LDS)
 // Measurement builds only (tools/b16w_epi_split.sh; the lists they return are wrong):
 // 1 = no per-tile epilogue (the stage loop alone), 2 = the screen without the insertions.  Both
 // hand every accumulator (and 2 the screen's masks) to an empty asm at each tile end, so the
@@ -210,7 +213,7 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
                      int dw, const uint32_t* __restrict__ qh, const float* __restrict__ qnorm, int nq,
                      int nsplit, int nqb, int64_t id_offset, float* __restrict__ cand_d,
                      int64_t* __restrict__ cand_i, int ncand, int ib, uint32_t* __restrict__ sync,
-                     uint32_t epoch, int lag) {
+                     uint32_t epoch, int lag, uint32_t* sbound) {
     __shared__ __attribute__((aligned(16))) char smem[kLDS];
 
     // XCD-aware bijective block -> (query block, row split) map, as knn_b16_tile_kernel
@@ -285,6 +288,27 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
             if constexpr (PACK) kp[h][p] = ~0u;
             else { kd[h][p] = INFINITY; ki[h][p] = -1; }
         }
+
+    // Shared screen bound (TileArgs::sbound, DESIGN.md "Shared screen bound").  For a tile (see
+    // rec_due) the wave copies the records of its kQW queries (2 KiB, contiguous) into LDS with two
+    // agent-scope LDS-DMA loads issued one stage before the tile's last, so they land under the
+    // stage loop's own wait and no register or memory wait is spent on them; the epilogue reads, per query,
+    // the slots (lane quarter lq: words 4 lq .. 4 lq + 3) and the limit coefficients.  U = the
+    // largest slot bounds the query's KM-th best approximate key over the whole corpus from above
+    // (the slots hold keys of rows of KM distinct row splits); +inf while a slot is empty.
+    // lu = the smallest L(U) seen so far and the value last published live per query in LDS
+    // (written by the query's lane of quarter 0, read by its four lanes: one wave, in order).
+    const bool sb_on = sbound != nullptr && IMGREC_B16W_NOPARK;
+    uint32_t* const wrec = sbound + (size_t)(qb * kBQ + wave * kQW) * kSBWords;    // wave-uniform
+    const uint32_t* const lrec = reinterpret_cast<const uint32_t*>(smem + kRecOff) + wave * (kQW * kSBWords);
+    uint2* const lst = reinterpret_cast<uint2*>(smem + kLuOff) + wave * kQW;
+    if (sb_on && lq == 0) {
+        lst[lc] = make_uint2(__float_as_uint(INFINITY), ~0u);
+        lst[lc + 16] = make_uint2(__float_as_uint(INFINITY), ~0u);
+    }
+    auto rec_dma = [&]() __attribute__((always_inline)) {
+        dma2_agent(wrec, smem0 + (uint32_t)(kRecOff + wave * (kQW * kSBWords * 4)), (uint32_t)lane * 16u);
+    };
 
     const int nst = dw / kBKW;
     const int total = (t1 - t0) * nst;
@@ -375,6 +399,10 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
         for (int rb = 0; rb < kRB; ++rb)
 #pragma unroll
             for (int h = 0; h < 2; ++h) acc[rb][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // the records are fetched for a split's first four tiles, then for every fourth: U falls
+        // like 1 / tiles done, and the corpus stream evicts the records from L2 between tiles, so
+        // each fetch is HBM traffic (a tile without one screens with the image it has)
+        const bool rec_due = sb_on && (t - t0 < 4 || ((t - t0) & 3) == 0);
         // live quad rows (64 tile rows each) of this tile: a split's partial last tile runs the
         // MFMAs, fragment reads and screens of its live row blocks only
         const int nlive = (t + 1) * kGPT <= cnt ? 4 : (((cnt - t * kGPT) * kRPP + 63) >> 6);
@@ -428,9 +456,11 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
                     if (isA) issue(g + 2);
                     else pend = g + 2;
                 }
+                if (rec_due && s + 2 == nst) rec_dma();
                 mfma_quad(acc, fa[1], fb[1], 4 + NR - 1);
             }
         };
+        if (rec_due && nst < 2) rec_dma();           // a one-stage tile: before its only wait
         if (nlive >= 4) stage_loop(std::integral_constant<int, 4>{});
         else if (nlive == 3) stage_loop(std::integral_constant<int, 3>{});
         else if (nlive == 2) stage_loop(std::integral_constant<int, 2>{});
@@ -452,6 +482,22 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
         const float* nrm = reinterpret_cast<const float*>(smem + kNormOff + ((t - t0) % kNormSlots) * kBM * 4);
         const bool full = (t + 1) * kGPT <= cnt && trow(t, kBM - 1) < nrows;
         auto row_ok = [&](int tr) { return t * kGPT + tr / kRPP < cnt && trow(t, tr) < nrows; };
+        float lu[2] = {INFINITY, INFINITY};
+        if (sb_on) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                // U and L(U) = U + (A + B |U|) >= prefix_limit(a) for every a <= U (the prep kernel
+                // inflated A, B: QueryBounds::limit_coefs); an empty slot (~0u), +inf or a NaN: no
+                // bound.  Words KM .. 11 of a record are 0; quarter 3 holds (A, B, floor, 0).
+                const uint4 c = *reinterpret_cast<const uint4*>(lrec + (lc + 16 * h) * kSBWords + 4 * lq);
+                const uint32_t ub = quarter_max_u(lq < 3 ? max(max(c.x, c.y), max(c.z, c.w)) : 0u);
+                const float cA = __uint_as_float(quarter_max_u(lq == 3 ? c.x : 0u));
+                const float cB = __uint_as_float(quarter_max_u(lq == 3 ? c.y : 0u));
+                const float U = ord_float(ub);
+                const float L = ub >= 0xff800000u ? INFINITY : U + fmaf(cB, fabsf(U), cA);
+                lu[h] = fminf(__uint_as_float(lst[lc + 16 * h].x), L);
+            }
+        }
         float cth[2];
         auto screen = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -459,6 +505,7 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
                 float T;
                 if constexpr (PACK) T = bucket_end(min(quarter_min_u(kp[h][KM - 1]), quarter_max_u(kp[h][kJ - 1])), lowm);
                 else T = fminf(quarter_min(kd[h][KM - 1]), quarter_max(kd[h][kJ - 1]));
+                T = fminf(T, lu[h]);
                 const float c = L2 ? 0.5f * (qn[h] - T) - kLo * (qn[h] + fabsf(T)) : -T;
                 cth[h] = qcol[h] < nq ? c : INFINITY;
             }
@@ -556,6 +603,26 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
             ins_cyc += __builtin_amdgcn_s_memtime() - ins0;
 #endif
         }
+        if (sb_on) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                // publish the best key of the query's four lists when it improved on the value
+                // last published: an upper bound of that row's approximate key (PACK: the end of
+                // its bucket), into the slot of this row split's residue class; one lane per
+                // query, pad queries never, an empty list (PACK: the increment wraps to 0) neither
+                const uint32_t best = quarter_min_u(PACK ? kp[h][0] : ord_bits(kd[h][0]));
+                uint32_t pubd = lst[lc + 16 * h].y;
+                const uint32_t pub = PACK ? (best | lowm) + 1u : best;
+                if (lq == 0) {
+                    if (qcol[h] < nq && pub != 0u && pub < 0xff800000u && pub < pubd) {
+                        __hip_atomic_fetch_min(sbound + (size_t)qcol[h] * kSBWords + split % KM, pub,
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        pubd = pub;
+                    }
+                    lst[lc + 16 * h] = make_uint2(__float_as_uint(lu[h]), pubd);
+                }
+            }
+        }
         B16W_STAMP(2 * (t - t0) + 1);
         // sibling lockstep (TileArgs::sync): publish this tile, wait (bounded) until the G
         // workgroups of this row split have all finished it (minus the lag), so they enter the
@@ -620,9 +687,15 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
         }
     }
     if (lq != 0) return;
+    const float lu[2] = {sb_on ? __uint_as_float(lst[lc].x) : INFINITY, sb_on ? __uint_as_float(lst[lc + 16].x) : INFINITY};
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if (qcol[h] >= nq) continue;
+        // the screen floor: lu only ever decreased, so its last value bounds from below every row
+        // this workgroup dropped by it (the rerank and the second chance fold it into their taus)
+        if (sb_on && lu[h] != INFINITY)
+            __hip_atomic_fetch_min(sbound + (size_t)qcol[h] * kSBWords + kSBFloor, ord_bits(lu[h]),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const size_t base = (size_t)qcol[h] * ncand + (size_t)split * KM;
 #pragma unroll
         for (int p = 0; p < KM; ++p) {
@@ -654,7 +727,7 @@ hipError_t launch_b16_wide(const TileArgs& a, hipStream_t st) {
 #define IMGREC_LAUNCH_B16W(KMV, L2V, PK)                                                             \
     hipLaunchKernelGGL((knn_b16w_tile_kernel<KMV, L2V, PK>), grid, block, 0, st, xh, a.xnorm,      \
                        a.nrows, a.dp, qh, a.qnorm, a.nq, a.nsplit, a.nqb, a.id_offset, a.cand_d,   \
-                       a.cand_i, a.ncand, a.ib, a.sync, a.epoch, a.sync_lag)
+                       a.cand_i, a.ncand, a.ib, a.sync, a.epoch, a.sync_lag, a.sbound)
 #define IMGREC_LAUNCH_B16W_K(KMV, PK)                                                               \
     do { if (a.metric == 1) IMGREC_LAUNCH_B16W(KMV, 1, PK); else IMGREC_LAUNCH_B16W(KMV, 0, PK); } while (0)
     if (a.km == 8) {

@@ -27,7 +27,8 @@ thread_local std::string g_err;
 }  // namespace
 
 // The A/B and test knobs read at index creation (IMGREC_CUS, IMGREC_I8_WGPCU, IMGREC_MERGE_FUSE,
-// IMGREC_CHANCE_SKIP, IMGREC_B16W_SYNC_LAG; INTEGRATION.md "A/B switches"): not product settings.
+// IMGREC_CHANCE_SKIP, IMGREC_B16W_SYNC_LAG, IMGREC_B16W_SHARED_BOUND; INTEGRATION.md "A/B
+// switches"): not product settings.
 // An inherited one silently re-plans every launch, so the first read of each that is set says so
 // once on stderr.
 const char* test_knob(const char* name) {
@@ -296,6 +297,7 @@ int create_single(int d, int metric, int device, knn_index** out) {
     if (const char* e = test_knob("IMGREC_RERANK_NW4")) ix->rerank_nw4 = *e != '0';
     if (const char* e = test_knob("IMGREC_MERGE_SINGLE")) ix->merge_single = *e != '0';
     if (const char* e = test_knob("IMGREC_STREAM_LISTS")) ix->stream_lists = *e != '0';
+    if (const char* e = test_knob("IMGREC_B16W_SHARED_BOUND")) ix->shared_bound = *e != '0';
     if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ix->fence, hipEventDisableTiming) != hipSuccess) {
         if (ix->stream) (void)hipStreamDestroy(ix->stream);
@@ -317,7 +319,7 @@ void free_single(knn_index* ix) {
     for (void* p : {(void*)ix->xh, (void*)ix->xr, (void*)ix->xr_max, (void*)ix->qb16,
                     (void*)ix->q_resid, (void*)ix->floor, (void*)ix->mws_d, (void*)ix->mws_i,
                     (void*)ix->mws_f, (void*)ix->stat, (void*)ix->fb_cd, (void*)ix->fb_ci,
-                    (void*)ix->b16_sync,
+                    (void*)ix->b16_sync, (void*)ix->sbound,
                     (void*)ix->tail_ctl, (void*)ix->chance, (void*)ix->sc_key, (void*)ix->sc_lab,
                     (void*)ix->sc_meta, (void*)ix->sc_done, (void*)ix->heads, (void*)ix->i8_dyn})
         if (p) (void)hipFree(p);

@@ -90,7 +90,49 @@ struct QueryBounds {
         return a_k + 2.02f * (bound_a(a_k) + bound_f(a_k) + trunc(a_k));
     }
     __device__ __forceinline__ float trunc(float a) const { return c_trunc * fabsf(a); }
+    // The bf16 bound from its inputs (the query prep kernels: no RerankArgs yet); the same
+    // expressions as the constructor above.
+    __device__ __forceinline__ QueryBounds(int metric_, float qn_, float xm_, float R, float dq,
+                                           float c_acc, float c_fp_, float c_trunc_) {
+        metric = metric_;
+        qn = qn_;
+        xm = xm_;
+        c_fp = c_fp_;
+        c_trunc = c_trunc_;
+        nn = sqrtf(qn) * sqrtf(xm) * (1.f + 1.0f / 1024.f) + 1e-30f;
+        const float sq = sqrtf(qn), X = sqrtf(xm);
+        e_ip = (sq * R + dq * (X + R) + c_acc * (sq + dq) * (X + R)) * (1.f + 1.0f / 256.f) + 1e-30f;
+    }
+    // prefix_limit is affine in |a|: prefix_limit(a) = a + A0 + B0 |a|.  The shared screen bound
+    // (knn_b16w.hip) evaluates L(U) = U + (A + B |U|) in fp32 with A = A0 (1 + 2^-8) and B = B0 (1 +
+    // 2^-8) + 32 u: the two roundings of L and the handful of prefix_limit cost at most a few u of
+    // |U| + A0 + B0 |U|, which 32 u |U| and 2^-8 (A0 + B0 |U|) cover, and B < 1 keeps L increasing
+    // for negative (inner-product) keys — so L(U) >= prefix_limit(a) for every a <= U.
+    __device__ __forceinline__ void limit_coefs(float& A, float& Bc) const {
+        const float infl = 1.f + 1.0f / 256.f;
+        if (metric == 1) {
+            A = 2.02f * (2.f * e_ip + 2.f * c_fp * nn + 4.f * u * (qn + xm)) * infl;
+            Bc = 2.02f * (4.f * u + c_trunc) * infl + 32.f * u;
+        } else {
+            A = 2.02f * (e_ip + c_fp * nn) * infl;
+            Bc = 2.02f * c_trunc * infl + 32.f * u;
+        }
+    }
 };
+
+// One wave's reset of a query's shared screen bound record (SharedBoundPrep; lanes 0 .. kSBWords -
+// 1 write one word each): every slot and the screen floor empty, the limit coefficients fresh,
+// the other words 0 (layout: knn_kernels.h kSBWords).
+__device__ __forceinline__ void shared_bound_reset(const SharedBoundPrep& sb, int64_t row, int lane,
+                                                   float qn, float dq) {
+    if (lane >= kSBWords) return;
+    const QueryBounds B(sb.metric, qn, *sb.xn_max, *sb.xr_max, dq, sb.c_acc, sb.c_fp, sb.c_trunc);
+    float A, Bc;
+    B.limit_coefs(A, Bc);
+    sb.rec[row * kSBWords + lane] = lane == kSBCoef ? __float_as_uint(A)
+                                  : lane == kSBCoef + 1 ? __float_as_uint(Bc)
+                                  : (lane < sb.km || lane == kSBFloor) ? ~0u : 0u;
+}
 
 // Rerank row loads (A/B): IMGREC_RERANK_NT=1 reads the candidate rows non-temporally (each is
 // read once per query; the int8 scan's non-temporal stream measured 13-15 % faster than the
@@ -165,6 +207,14 @@ __device__ __forceinline__ float rerank_key(float ip, float qn, float xnr, int m
     return -ip;
 }
 
+
+// The smallest key a row dropped by the candidate kernel's shared screen bound can have (+inf:
+// none was, or the bound is off).  Written by atomics of the candidate launch, read after it.
+__device__ __forceinline__ float screen_floor(const RerankArgs& a, int64_t q) {
+    if (!a.sbound) return INFINITY;
+    const uint32_t f = a.sbound[q * kSBWords + kSBFloor];
+    return f == 0xffffffffu ? INFINITY : key_from_ordered(f);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Cross-workgroup hand-off (MI355X_MICROARCH.md "Valid forms"): producer = every storing wave's
@@ -495,7 +545,8 @@ __device__ __forceinline__ int second_chance_slice(const RerankArgs& a, int item
     const int flag = L.s_flag;
     // +inf floor: no list dropped a row, so every row was a candidate and the slices hold all
     // that can matter
-    const float tauL = tbm == 0xffffffffu ? INFINITY : key_from_ordered(tbm);
+    // (and the candidate kernel's screen floor: rows its shared bound dropped sit in no list)
+    const float tauL = fminf(tbm == 0xffffffffu ? INFINITY : key_from_ordered(tbm), screen_floor(a, q));
     const bool ok = flag == 0 && (tauL == INFINITY || (tauL - B.bound_a(tauL)) > (L.s_sk + B.bound_f(L.s_sk)));
     if (ok) {
         if (t < k) {

@@ -126,6 +126,9 @@ struct knn_index {
     int* i8_dyn = nullptr;      // the pool's two counters (zeroed once; the scan leaves them at 0)
     bool stream_lists = true;   // exact lists of <= 4 queries from one fp32 stream (IMGREC_STREAM_LISTS=0: tiles)
     bool merge_single = false;  // IMGREC_MERGE_SINGLE=1: the single-level merge in the rerank
+    // IMGREC_B16W_SHARED_BOUND=0: the 256 x 256 bf16 kernel's lists screen each on their own (no
+    // shared per-query bound, TileArgs::sbound)
+    bool shared_bound = true;
     bool rerank_nw4 = false;    // IMGREC_RERANK_NW4=1: large batches rerank on 4-wave workgroups
     bool rerank_p1k = true;     // large batches rerank k rows first (IMGREC_RERANK_P1=0: 16)
     bool i8_fused_prep = true;  // int8 query prep inside the scan (IMGREC_I8_FUSED_PREP=0: own launch)
@@ -191,6 +194,7 @@ struct knn_index {
     float* mws_f = nullptr; size_t mws_f_cap = 0;
     uint32_t* b16_sync = nullptr; size_t b16_sync_cap = 0;   // 256 x 256 kernel sibling progress
     uint32_t b16_epoch = 0;
+    uint32_t* sbound = nullptr; size_t sbound_cap = 0;       // shared screen bound records (kSBWords per query)
     size_t xr_max_cap = 0;
     // exact re-run workspace (device-planned: queries, candidate lists, plan)
     float* fb_q = nullptr; size_t fb_q_cap = 0;

@@ -38,6 +38,29 @@ struct TileArgs {
     uint32_t* sync = nullptr;
     uint32_t epoch = 0;
     int sync_lag = 0;           // tiles a workgroup may run ahead of its slowest sibling
+    // 256 x 256 bf16 kernel, optional: the shared screen bound's per-query records (nq_pad x
+    // kSBWords, reset by the query prep: SharedBoundPrep); NULL = every list screens alone
+    uint32_t* sbound = nullptr;
+};
+
+// Shared screen bound of the 256 x 256 bf16 kernel (knn_b16w.hip, DESIGN.md "Shared screen
+// bound"): one record of kSBWords u32 per padded query.  Words 0 .. KM - 1: slot s % KM holds the
+// smallest upper bound of a real row's approximate key that the workgroups of the row splits s, s +
+// KM, ... have published (order-preserving key bits, ~0u = none yet); words KM .. 11: 0 (neutral
+// in the kernel's maximum over a 4-word group); words kSBCoef, kSBCoef + 1: the float
+// coefficients A, B (both > 0) of L(U) = U + A + B |U| >= QueryBounds::prefix_limit(a) for every
+// a <= U; word kSBFloor: the smallest shared threshold any workgroup screened the query with (key
+// bits, ~0u = none; the certificate's screen floor); word 15: 0.
+constexpr int kSBWords = 16, kSBCoef = 12, kSBFloor = 14;
+
+// What the query prep kernels need to reset a chunk's records and write the coefficients.
+struct SharedBoundPrep {
+    uint32_t* rec = nullptr;    // nq_pad x kSBWords; NULL = nothing to do
+    const float* qnorm = nullptr;   // |q|^2 per row (launch_bf16_rows only: its kernel has none)
+    const float* xn_max = nullptr;  // device scalars, as RerankArgs
+    const float* xr_max = nullptr;
+    float c_acc = 0.f, c_fp = 0.f, c_trunc = 0.f;   // RerankArgs::c_split, c_fp, c_trunc
+    int metric = 0, km = 0;     // km: the candidate kernel's list length = slots per query
 };
 
 // One rerank + certificate launch over merged candidate-pass candidates (knn_refine.hip).
@@ -66,6 +89,9 @@ struct RerankArgs {
                                 // kModeI8: max over rows of |x - s c| (the int8 copy's residual)
     float* floor;               // per query: smallest key any row outside the candidates can
                                 // have besides the K'-th candidate's (merge "floor"), or NULL
+    // the candidate kernel's shared screen bound records (TileArgs::sbound), or NULL: word kSBFloor
+    // of query q's record bounds every row that bound dropped from below; folded into every tau
+    const uint32_t* sbound = nullptr;
     // the candidate merge's second level fused into the rerank (launch_merge_candidates with
     // defer_level2; small batches): per query l1_G lists of 16 (key, label) at l1_d / l1_i +
     // q * l1_G * 16 and their floors at l1_floor + q * l1_G; wave 0 selects the kc best and writes
@@ -195,6 +221,12 @@ constexpr int kB16NS = IMGREC_B16_NS, kB16WGPCU = IMGREC_B16_WGPCU, kB16Pad = 64
 #endif
 constexpr int kB16PackMaxIB = IMGREC_B16_PACK_MAXIB;
 constexpr int kB16BigRows = 256, kB16BigQueries = 256, kB16BigMinQ = IMGREC_B16_BIG_MINQ;
+// The shared screen bound's LDS image takes the place of knn_b16w.hip's insertion park (round 6's
+// A/B switch, off by default): a build with the park, or on the 32 x 32 kernel, has no bound.
+#ifndef IMGREC_B16W_NOPARK
+#define IMGREC_B16W_NOPARK 1
+#endif
+constexpr bool kSharedBoundBuilt = IMGREC_B16_MFMA16 != 0 && IMGREC_B16W_NOPARK != 0;
 
 // Small-batch candidate pass on the block-scaled int8 copy (knn_i8.hip): per (query, row split)
 // the km best approximate keys, nq <= 8 queries in one launch, nsplit workgroups.
@@ -301,13 +333,14 @@ hipError_t launch_gather_rows(const float* src, const float* src_norm, int dp, c
 hipError_t launch_scatter_results(const float* sd, const int64_t* si, const int* list, int64_t n,
                                   int k, float* D, int64_t* I, hipStream_t st);
 // fp32 rows (stride dp) -> bf16 rows (stride dpb elements, zero padded), |x - bf16(x)| per row
+// (sb: query rows of the 256 x 256 kernel — the shared screen bound's records are reset too)
 hipError_t launch_bf16_rows(const float* src, int64_t n, int dp, int dpb, uint16_t* dst,
-                            float* resid, hipStream_t st);
+                            float* resid, hipStream_t st, const SharedBoundPrep* sb = nullptr);
 // bf16 path query side in one pass: padded fp32 rows + |q|^2 + bf16 rows + residual norms
 // (dpb <= 4096; hipErrorInvalidValue otherwise, the caller then uses the two kernels above)
 hipError_t launch_query_prep_b16(const float* src, int64_t n, int d, int dp, int dpb, int64_t n_pad,
                                  int normalize, float* dst, float* norms, uint16_t* qb, float* resid,
-                                 hipStream_t st);
+                                 hipStream_t st, const SharedBoundPrep* sb = nullptr);
 hipError_t launch_max_norm(const float* xn, int64_t n, float* out, hipStream_t st);
 
 // IVF-PQ (ivfpq.hip; layouts in include/imgrec_ivfpq.h)

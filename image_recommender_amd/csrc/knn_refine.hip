@@ -73,7 +73,7 @@ split_rows_kernel(const float* __restrict__ src, int64_t n, int dp, int bk,
 // certificate inflates it, knn_capi.cpp bf16 bound).
 __global__ void __launch_bounds__(256)
 bf16_rows_kernel(const float* __restrict__ src, int64_t n, int dp, int dpb,
-                 uint16_t* __restrict__ dst, float* __restrict__ resid) {
+                 uint16_t* __restrict__ dst, float* __restrict__ resid, const SharedBoundPrep sb) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= n) return;
@@ -106,6 +106,7 @@ bf16_rows_kernel(const float* __restrict__ src, int64_t n, int dp, int dpb,
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
     if (lane == 0) resid[row] = sqrtf(acc);
+    if (sb.rec) shared_bound_reset(sb, row, lane, sb.qnorm[row], sqrtf(acc));
 }
 
 // One wave per query row, the bf16 path's whole query side in one pass: raw row (d floats) ->
@@ -117,7 +118,7 @@ __global__ void __launch_bounds__(256)
 query_prep_b16_kernel(const float* __restrict__ src, int64_t n, int d, int dp, int dpb,
                       int64_t n_pad, int normalize, float* __restrict__ dst,
                       float* __restrict__ norms, uint16_t* __restrict__ qb,
-                      float* __restrict__ resid) {
+                      float* __restrict__ resid, const SharedBoundPrep sb) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= n_pad) return;
@@ -186,6 +187,8 @@ query_prep_b16_kernel(const float* __restrict__ src, int64_t n, int d, int dp, i
         norms[row] = nacc;
         resid[row] = sqrtf(racc);
     }
+    // the candidate kernel's shared screen bound: this query's record starts empty
+    if (sb.rec) shared_bound_reset(sb, row, lane, nacc, sqrtf(racc));
 }
 
 // One workgroup of kRerankWaves waves per query.  a.cd/a.ci: the merged approximate candidates,
@@ -453,6 +456,9 @@ rerank_certify_kernel(const RerankArgs a) {
     const bool valid = lab >= 0;
     const int nvalid = __popcll(__ballot(valid));               // valid candidates come first
     const QueryBounds B(a, q);
+    // rows the candidate kernel's shared screen bound dropped were dropped by no list: their
+    // floor joins every tau below, whichever merge form ran (launched, l1_G / l0_lists, s_lists)
+    const float sfloor = screen_floor(a, q);
 
     // A query whose K' candidates all sit inside the band this certificate needs (tau - E_a(tau)
     // at most a quarter bound above the k-th approximate key, tau = min(K'-th candidate, floor))
@@ -464,6 +470,7 @@ rerank_certify_kernel(const RerankArgs a) {
         float tau0 = __shfl(ak, kc - 1, 64);
         if (fused) tau0 = fminf(tau0, s_floor);
         else if (a.floor) tau0 = fminf(tau0, a.floor[q]);
+        tau0 = fminf(tau0, sfloor);
         if (tau0 - B.bound_a(tau0) <= a_kk + 0.25f * B.bound_a(a_kk)) {
             if (threadIdx.x == 0) {
                 atomicAdd(a.stats + 2, 1);
@@ -574,6 +581,7 @@ rerank_certify_kernel(const RerankArgs a) {
     float tau = (lab_tau >= 0 && nvalid >= kc) ? __shfl(ak, kc - 1, 64) : INFINITY;
     if (fused) tau = fminf(tau, s_floor);
     else if (a.floor) tau = fminf(tau, a.floor[q]);
+    tau = fminf(tau, sfloor);
     const float a_out = __shfl(ak, min(m, 63), 64);
     if (m < nvalid) tau = fminf(tau, a_out);
     bool failed = false;                            // tau = +inf: every row was reranked
@@ -703,22 +711,24 @@ hipError_t launch_scatter_results(const float* sd, const int64_t* si, const int*
 }
 
 hipError_t launch_bf16_rows(const float* src, int64_t n, int dp, int dpb, uint16_t* dst,
-                            float* resid, hipStream_t st) {
+                            float* resid, hipStream_t st, const SharedBoundPrep* sb) {
     if (n <= 0) return hipSuccess;
     if (dpb % 8 != 0 || dp % 8 != 0 || dpb < dp) return hipErrorInvalidValue;
+    if (sb && sb->rec && !sb->qnorm) return hipErrorInvalidValue;
     hipLaunchKernelGGL(bf16_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, src, n, dp,
-                       dpb, dst, resid);
+                       dpb, dst, resid, sb ? *sb : SharedBoundPrep{});
     return hipGetLastError();
 }
 
 hipError_t launch_query_prep_b16(const float* src, int64_t n, int d, int dp, int dpb, int64_t n_pad,
                                  int normalize, float* dst, float* norms, uint16_t* qb, float* resid,
-                                 hipStream_t st) {
+                                 hipStream_t st, const SharedBoundPrep* sb) {
     if (n_pad <= 0) return hipSuccess;
     if (dpb % 8 != 0 || dp % 16 != 0 || dpb < dp || dp < d) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((n_pad + 3) / 4)), block(256);
 #define IMGREC_QPREP(ITV) hipLaunchKernelGGL((query_prep_b16_kernel<ITV>), grid, block, 0, st, src, n, \
-                                             d, dp, dpb, n_pad, normalize, dst, norms, qb, resid)
+                                             d, dp, dpb, n_pad, normalize, dst, norms, qb, resid,      \
+                                             sb ? *sb : SharedBoundPrep{})
     if (dpb <= 512) IMGREC_QPREP(1);
     else if (dpb <= 1024) IMGREC_QPREP(2);
     else if (dpb <= 2048) IMGREC_QPREP(4);

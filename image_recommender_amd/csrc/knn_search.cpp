@@ -238,6 +238,29 @@ int b16_sync_lag() {
     return v;
 }
 
+// The shared screen bound of a chunk that runs the 256 x 256 16x16-MFMA kernel (knn_b16w.hip): grows
+// the index's per-query records and fills what the query prep kernel needs to reset them (sb->rec
+// stays NULL for every other plan, and with IMGREC_B16W_SHARED_BOUND=0).  The prep reads the corpus
+// maxima, so they are refreshed here, ahead of it.
+int shared_bound_prep(knn_index* ix, const Plan& p, const float* qnorm, hipStream_t st,
+                      SharedBoundPrep* sb) {
+    *sb = SharedBoundPrep{};
+    if (!ix->shared_bound || !p.big || !kSharedBoundBuilt) return KNN_OK;
+    int rc;
+    if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
+    if ((rc = grow(&ix->sbound, &ix->sbound_cap, (size_t)p.nq_pad * kSBWords)) != KNN_OK) return rc;
+    sb->rec = ix->sbound;
+    sb->qnorm = qnorm;
+    sb->xn_max = ix->xn_max;
+    sb->xr_max = ix->xr_max;
+    sb->c_acc = b16_acc_coef(ix->dpb);
+    sb->c_fp = rerank_coef(ix->dp);
+    sb->c_trunc = p.ib > 0 ? (float)std::ldexp(1.0, p.ib - 23) : 0.f;
+    sb->metric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    sb->km = p.km;
+    return KNN_OK;
+}
+
 // bf16 candidates (one bf16 MFMA per product) + exact fp32 rerank of K' = 64 + certificate.
 int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,
               int64_t* I, hipStream_t st, bool timed, bool q_ready, bool first) {
@@ -255,8 +278,11 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     if ((rc = grow(&ix->cand2_i, &ix->cand2_i_cap, (size_t)nq * kc)) != KNN_OK) return rc;
     if ((rc = grow(&ix->floor, &ix->floor_cap, (size_t)nq)) != KNN_OK) return rc;
     if ((rc = grow_stats(ix, nq, st)) != KNN_OK) return rc;
+    // (the prep — here or search_locked's — also resets the shared screen bound's records)
+    SharedBoundPrep sb;
+    if ((rc = shared_bound_prep(ix, p, qnorm, st, &sb)) != KNN_OK) return rc;
     if (!q_ready)   // else search_locked's fused query prep already wrote qb16 / q_resid
-        KNN_HIP(launch_bf16_rows(qpad, p.nq_pad, ix->dp, ix->dpb, ix->qb16, ix->q_resid, st));
+        KNN_HIP(launch_bf16_rows(qpad, p.nq_pad, ix->dp, ix->dpb, ix->qb16, ix->q_resid, st, &sb));
     TileArgs a{};
     a.wr = p.wr; a.wq = p.wq; a.km = km; a.wb = kB16WB; a.mode = kModeBF16;
     a.xb = reinterpret_cast<const float*>(ix->xh); a.xnorm = ix->xn; a.nrows = (int)ix->ntotal;
@@ -264,6 +290,7 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     a.nq = (int)nq; a.metric = kmetric; a.ntiles = p.ntiles; a.nsplit = p.nsplit; a.nqb = p.nqb;
     a.id_offset = ix->id_offset; a.cand_d = ix->cand_d; a.cand_i = ix->cand_i; a.ncand = p.ncand;
     a.ib = p.big ? p.ib : 0;
+    a.sbound = sb.rec;
     if (p.big && b16_sync_lag() >= 0) {
         // sibling lockstep of the 256 x 256 kernel: progress slots zeroed once, a new epoch per
         // launch (values of earlier launches compare as "not yet")
@@ -304,6 +331,7 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     r.c_fp = rerank_coef(ix->dp); r.D = D; r.I = I;
     r.c_trunc = a.ib > 0 ? (float)std::ldexp(1.0, a.ib - 23) : 0.f;
     r.q_resid = ix->q_resid; r.xr_max = ix->xr_max; r.floor = ix->floor;
+    r.sbound = a.sbound;
     if (l1G > 0) { r.l1_d = ix->mws_d; r.l1_i = ix->mws_i; r.l1_floor = ix->mws_f; r.l1_G = l1G; }
     if (l0) r.l0_lists = nlists;
     r.raw_d = ix->cand_d; r.raw_i = ix->cand_i; r.raw_lists = nlists; r.raw_km = km;
@@ -566,8 +594,11 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
         } else if (b16 && ix->dpb <= 4096) {
             if ((rc = grow(&ix->qb16, &ix->qb16_cap, (size_t)nq_pad * ix->dpb)) != KNN_OK) return rc;
             if ((rc = grow(&ix->q_resid, &ix->q_resid_cap, (size_t)nq_pad)) != KNN_OK) return rc;
+            SharedBoundPrep sb;
+            if ((rc = shared_bound_prep(ix, p, ix->qnorm, st, &sb)) != KNN_OK) return rc;
             KNN_HIP(launch_query_prep_b16(q + c0 * ix->d, cn, ix->d, ix->dp, ix->dpb, nq_pad,
-                                          normalize, ix->qpad, ix->qnorm, ix->qb16, ix->q_resid, st));
+                                          normalize, ix->qpad, ix->qnorm, ix->qb16, ix->q_resid, st,
+                                          &sb));
             q_ready = true;
         } else {
             KNN_HIP(launch_rows_ingest(q + c0 * ix->d, cn, ix->d, ix->dp, nq_pad, normalize,

@@ -62,6 +62,21 @@ __device__ __forceinline__ void dma4_norm(const float* g, uint32_t lds) {
         : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
 }
 
+// 2 KiB (two one-KiB pieces, lane l: bytes 16 l .. 16 l + 15 of each) read at agent scope (sc1:
+// past the L1, as a relaxed agent-scope atomic load is): words other workgroups update with
+// atomics during the launch; every aligned dword arrives whole
+__device__ __forceinline__ void dma2_agent(const void* sbase, uint32_t lds0, uint32_t v) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, %2 sc1\n\t"
+        "global_load_lds_dwordx4 %1, %2 offset:1024 sc1\n\t"
+        "s_mov_b32 m0, %0"
+        : "=&s"(keep)
+        : "v"(v), "s"(sbase), "s"(__builtin_amdgcn_readfirstlane(lds0))
+        : "memory");
+}
+
 __device__ __forceinline__ void barrier_lds() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");

@@ -1,29 +1,59 @@
-// knn_b16w.hip — 256 x 256-tile bf16 candidate kernel on v_mfma_f32_16x16x32_bf16 (gfx950).
+// knn_b16w.hip — the 256 x 256-tile bf16 candidate kernel of the k-NN search, on
+// v_mfma_f32_16x16x32_bf16 (gfx950 / MI355X).
 //
-// Same contract, launch plan, LDS ring and DMA schedule as knn_b16_tile_kernel (knn_b16.hip):
-// score every corpus row of the workgroup's row split against a block of 256 queries with one
-// bf16 MFMA per product (fp32 accumulation) and keep, per (query, row split), the KM best
-// approximate keys; knn_refine.hip reranks and certifies the merged candidates.  It replaces the
-// arithmetic of faiss IndexFlat.search reached from main/search_from_image.py:247.
+// Contract: score every corpus row of the workgroup's row split against a block of 256 queries
+// with one bf16 MFMA per product (fp32 accumulation) and keep, per (query, row split), the KM best
+// approximate keys in registers; knn_refine.hip reranks and certifies the merged candidates.  It
+// replaces the arithmetic of faiss IndexFlat.search reached from main/search_from_image.py:247.
 //
-// Why a 16 x 16 MFMA form: in a power-limited MFMA loop the chip holds a higher clock on
-// v_mfma_f32_16x16x32_bf16 than on v_mfma_f32_32x32x16_bf16 at equal cycles per flop
-// (MI355X_MICROARCH.md, DVFS give-back item 7), and the 32 x 32 kernel runs at ~1.67 GHz.
+// Why a kernel of its own: the 128 x 128 tile of the generic kernel (knn_kernels.hip) stages
+// 2 bytes of LDS-DMA per MFMA; at one workgroup per CU a 256 x 256 tile halves the staged bytes
+// (2 N D Q (1/BM + 1/BQ)).  Why the 16 x 16 MFMA form: in a power-limited MFMA loop the chip holds
+// a higher clock on v_mfma_f32_16x16x32_bf16 than on v_mfma_f32_32x32x16_bf16 at equal cycles per
+// flop (MI355X_MICROARCH.md, DVFS give-back item 7).
 //
 // Geometry: 8 waves along the queries; wave w owns queries 32w .. 32w + 31 of the block (two
 // 16-query MFMA blocks) against all 256 rows of the tile (sixteen 16-row blocks): 32 MFMAs per
 // 32-deep k-step, 128 accumulator registers per lane.  With the 16 x 16 accumulator map (col =
 // lane & 15 -> query, row = 4 (lane >> 4) + reg) each lane owns two queries and 64 rows of each,
-// so the top-k keeps two register lists per lane as the 32 x 32 kernel does; the four lanes of
+// so the top-k keeps two register lists per lane and needs no data movement; the four lanes of
 // a query (one per lane quarter) hold its four lists, so the screen's shared bound and the final
 // fold are wave-local shuffles (no LDS share region, no cross-wave fold).
 //
-// Stage = 64 bf16 of depth per row (two 32-deep k-steps) for 256 rows + 256 queries, two-slot
-// ring, same LDS image and XOR swizzle as knn_b16.hip (row r, 16-B chunk c at c ^ ((r >> 1) & 7)).
-// k-step c of lane quarter lq reads logical chunk 4c + lq of row (lane & 15) of a 16-row block:
-// the ds_read_b128 lane groups then hit 16 distinct bank slots.  A stage's 64 MFMAs run as 8
-// quads (4 row blocks x 2 query blocks each); the next quad's fragments are read under the
-// current quad's MFMAs, one read per MFMA gap; the barrier sits before the last quad.
+// LDS image: a stage = 64 bf16 of depth per row (128 B, two 32-deep k-steps) for 256 rows (A) +
+// 256 queries (B) = 64 KiB, in a two-slot ring (128 KiB), then a four-tile ring of row norms, the
+// waves' shared-bound records and the per-query screen state (150 KiB in all).  Row r of a stage
+// keeps its 16-B chunk c at chunk c ^ ((r >> 1) & 7) (two 128-B rows per 256-B bank row); the XOR
+// is applied on the DMA's per-lane global source offset.  k-step c of lane quarter lq reads
+// logical chunk 4c + lq of row (lane & 15) of a 16-row block, so every ds_read_b128 lane group of
+// 16 hits 16 distinct bank slots.
+//
+// Row splits: the corpus is cut into groups of kRPP = 8 rows (one DMA piece each); split s owns
+// the global groups s, s + nsplit, s + 2 nsplit, ... and a tile holds kGPT consecutive groups of
+// its split.  The splits are interleaved because a stored order that keeps similar rows together
+// (the reference stores images folder by folder) is thereby spread over every split, so no
+// split's short list has to hold most of a query's neighbours — with contiguous splits the merge
+// floor bound on such corpora and sent a quarter of the queries to the exact re-run.
+//
+// DMA: each wave moves 8 one-KiB pieces per stage (waves 0-3 the corpus tile, 4-7 the query tile)
+// with global_load_lds_dwordx4 in the saddr form (lds_dma.h): one per-piece 32-bit lane offset
+// fixed for the whole launch, one scalar base per stage, one M0 write per four pieces (the
+// instruction offset j KiB moves both the global source and the LDS destination, so the lane
+// offsets are pre-reduced by j KiB).  A tile's corpus pieces sit nsplit * kRPP rows apart: the
+// lane offsets stay fixed and the scalar base moves by kGPT groups per tile.  Pieces are kPS bytes
+// apart and the swizzle of a piece's rows depends only on the piece's parity, so a lane keeps two
+// bases and piece j's offset is vpar[j & 1] + (j & ~1) kPS - 1024 (j & 3).
+//
+// Schedule: a stage's 64 MFMAs run as 8 quads (4 row blocks x 2 query blocks each); the next
+// quad's fragments are read under the current quad's MFMAs, one read per MFMA gap.  One barrier
+// per stage, before its last quad: by then every wave has read the whole stage (its slot is
+// refilled with stage g + 2 right after) and waited for its own DMA of stage g + 1, so the next
+// stage's first fragments are read after the barrier while the last quad's MFMAs run and the MFMA
+// pipe does not drain.  The corpus-tile waves issue the DMA of stage g + 2 right after the
+// barrier, the query-tile waves (static priority 1: the younger half loses issue arbitration
+// otherwise) kDeferQ quads later, so each SIMD's MFMA pipe has a feeder during either wave's DMA
+// issue.  After a tile's last stage the top-k epilogue runs without barriers (it touches no stage
+// memory).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,13 +90,13 @@ constexpr int kStage = kSA + kSB;
 constexpr int kLPW = (kBM + kBQ) / kRPP / kNW;   // DMA pieces per wave per stage
 constexpr int kNormSlots = 4;             // row-norm ring (tiles)
 constexpr int kNormOff = kNS * kStage;
-constexpr int kParkOff = kNormOff + kNormSlots * kBM * 4;   // per wave: 8 accumulators per lane
-// shared screen bound: a wave's kQW query records (kSBWords words each: 2 KiB, by LDS-DMA) take
-// the park's place, and per query (lu, last published value) follows
-constexpr int kRecOff = kParkOff;
-constexpr int kLuOff = kParkOff + kNW * 64 * 8 * 4;
+// shared screen bound: per wave its kQW query records (kSBWords words each: 2 KiB, two LDS-DMA
+// pieces), then per query (lu, last published value)
+constexpr int kRecOff = kNormOff + kNormSlots * kBM * 4;
+constexpr int kLuOff = kRecOff + kNW * kQW * kSBWords * 4;
 constexpr int kLDS = kLuOff + kBQ * 2 * 4;
-static_assert(kQW * kSBWords * 4 == 64 * 8 * 4 && kSBWords == 16, "a wave's records fill its park area");
+static_assert(kQW * kSBWords * 4 == 2048 && kSBWords == 16, "a wave's records: one dma2_agent of 2 KiB");
+static_assert(kLDS == 153600, "LDS image");
 constexpr int kQuads = 8;                 // MFMA quads per stage (2 k-steps x 4)
 // the query-tile waves issue their DMA after this quad of the next stage (the corpus-tile waves
 // issue theirs right after the barrier), so each SIMD's other wave feeds the MFMA pipe meanwhile
@@ -78,12 +108,9 @@ static_assert(kBKW == 32 && kCPR == 8, "stage depth: two 32-deep k-steps per sta
 static_assert(kLDS <= 160 * 1024, "LDS budget");
 static_assert(kLPW % 4 == 0, "pieces go out in dma4x groups of four");
 static_assert(kDeferQ >= 0 && kDeferQ < kQuads - 1, "deferred DMA inside the stage's first quads");
-// Insertion without the LDS park (round 6 default; =0 restores the park for A/B): a passing row's
-// accumulator and norm are picked from the registers of its two row blocks by a 3-level
-// v_cndmask tree instead of a ds_write / ds_read round trip per row (the norms stay in the
-// registers the screen loaded them into).  Bit-identical; cfg2 0.3-1.2 % faster, cfg3 the same
-// (profiles/r06/nopark/).
-// (the default, 1, is set in knn_kernels.h: the shared screen bound needs the park's LDS)
+// Insertion: a passing row's accumulator and norm are picked from the registers of its two row
+// blocks by a 3-level v_cndmask tree (sel8; the norms stay in the registers the screen loaded
+// them into), with no trip through LDS.
 // Measurement builds only (tools/b16w_epi_split.sh; the lists they return are wrong):
 // 1 = no per-tile epilogue (the stage loop alone), 2 = the screen without the insertions.  Both
 // hand every accumulator (and 2 the screen's masks) to an empty asm at each tile end, so the
@@ -212,11 +239,11 @@ __global__ void __launch_bounds__(512, 2)
 knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ xnorm, int nrows,
                      int dw, const uint32_t* __restrict__ qh, const float* __restrict__ qnorm, int nq,
                      int nsplit, int nqb, int64_t id_offset, float* __restrict__ cand_d,
-                     int64_t* __restrict__ cand_i, int ncand, int ib, uint32_t* __restrict__ sync,
-                     uint32_t epoch, int lag, uint32_t* sbound) {
+                     int64_t* __restrict__ cand_i, int ncand, int ib, uint32_t* sbound) {
     __shared__ __attribute__((aligned(16))) char smem[kLDS];
 
-    // XCD-aware bijective block -> (query block, row split) map, as knn_b16_tile_kernel
+    // XCD-aware bijective block -> (query block, row split) map: the G query blocks of one row
+    // split run on one XCD and share its L2 for the corpus tiles
     const int nwg = gridDim.x, wg = blockIdx.x;
 #ifdef IMGREC_B16_STAMPS
     if (threadIdx.x == 0 && wg < 1024) g_b16w_wg[2 * wg] = __builtin_amdgcn_s_memrealtime();
@@ -228,9 +255,8 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
     const int qbg = wgid / (nsplit * G), rem = wgid - qbg * (nsplit * G);
     const int split = rem / G;
     const int qb = qbg * G + rem % G;
-    // the G query-block workgroups of this row split: wgids sib0 .. sib0 + G - 1
-    const int sib0 = wgid - rem % G;
-    bool sync_on = sync != nullptr && G == kG;
+    // this split's rows (header): cnt groups, global group split + m * nsplit for m < cnt; trow =
+    // stored row of tile row tr of tile t (groups past the split's end: the tile's first group)
     const int ngroups = (nrows + kRPP - 1) / kRPP;
     const int cnt = split < ngroups ? (ngroups - split + nsplit - 1) / nsplit : 0;
     const int t0 = 0, t1 = (cnt + kGPT - 1) / kGPT;
@@ -249,7 +275,8 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
     if (L2) { qn[0] = qnorm[qcol[0]]; qn[1] = qnorm[qcol[1]]; }
     asm volatile("" : "+v"(qn[0]), "+v"(qn[1]));
 
-    // ---- DMA (as knn_b16.hip): waves 0-3 move the corpus tile, 4-7 the query tile
+    // ---- DMA (header): waves 0-3 move the corpus tile, 4-7 the query tile; lane -> (row prow of
+    // the piece, chunk pchk), source chunk pre-swizzled
     const bool isA = wave < 4;
     if (!isA) __builtin_amdgcn_s_setprio(1);
     const int pbase = (isA ? wave : wave - 4) * kLPW;
@@ -298,7 +325,7 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
     // (the slots hold keys of rows of KM distinct row splits); +inf while a slot is empty.
     // lu = the smallest L(U) seen so far and the value last published live per query in LDS
     // (written by the query's lane of quarter 0, read by its four lanes: one wave, in order).
-    const bool sb_on = sbound != nullptr && IMGREC_B16W_NOPARK;
+    const bool sb_on = sbound != nullptr;
     uint32_t* const wrec = sbound + (size_t)(qb * kBQ + wave * kQW) * kSBWords;    // wave-uniform
     const uint32_t* const lrec = reinterpret_cast<const uint32_t*>(smem + kRecOff) + wave * (kQW * kSBWords);
     uint2* const lst = reinterpret_cast<uint2*>(smem + kLuOff) + wave * kQW;
@@ -355,8 +382,6 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
 
     constexpr int kJ = (KM + 3) / 4;
     constexpr float kLo = 1.0f / 1048576.f;
-    float4* const park = reinterpret_cast<float4*>(smem + kParkOff) + wave * (2 * 64);
-    const float* const pk = reinterpret_cast<const float*>(park);
 
     // quad q of a stage: k-step q >> 2, row blocks 4 (q & 3) .. + 3
     auto read_a = [&](const char* sb, int q, u32x4 (&fa)[4]) __attribute__((always_inline)) {
@@ -470,8 +495,12 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
         // K-th of any of the query's four lane lists, max over them of their J-th best) — four
         // lists holding J >= KM/4 entries each at or below that max give the union KM better
         // entries, and a dropped row ranks behind the folded list's last entry (merge floor).
-        // The test runs on the accumulator (see knn_b16.hip): d = (|x|^2 (1/2 - 2^-20) + c) - acc
-        // with c = (|q|^2 - T)/2 - 2^-20 (|q|^2 + |T|) is negative iff the row passes.
+        // The test runs on the accumulator, so a row that fails costs no key: d = (|x|^2 (1/2 -
+        // 2^-20) + c) - acc with c = (|q|^2 - T)/2 - 2^-20 (|q|^2 + |T|) is negative iff the row
+        // passes (the 2^-20 terms keep fp32 rounding from rejecting a row the exact key would
+        // keep); two packed adds per pair of rows and one v_alignbit per row shift the sign bits
+        // into a 16-bit lane mask per 64-row group.  A lane's passing rows are then visited one
+        // per round, keyed and inserted.
         B16W_STAMP(2 * (t - t0));
 #if IMGREC_B16W_EPI_EXP != 0
 #pragma unroll
@@ -559,11 +588,6 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
                     unsigned mh = (m >> (8 * hf)) & 0xffu;
                     if (!__any(mh != 0)) continue;
                     const int rb0 = 4 * rg + 2 * hf;
-#if !IMGREC_B16W_NOPARK
-                    park[lane] = make_float4(acc[rb0][h][0], acc[rb0][h][1], acc[rb0][h][2], acc[rb0][h][3]);
-                    park[64 + lane] = make_float4(acc[rb0 + 1][h][0], acc[rb0 + 1][h][1],
-                                                  acc[rb0 + 1][h][2], acc[rb0 + 1][h][3]);
-#endif
                     while (__any(mh != 0)) {
 #ifdef IMGREC_B16_STAMPS
                         ++nit;
@@ -572,16 +596,11 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
                         const int r8 = act ? __builtin_ctz(mh) : 0;
                         mh &= mh - 1u;
                         const int tr = (rb0 + (r8 >> 2)) * 16 + 4 * lq + (r8 & 3);
-#if IMGREC_B16W_NOPARK
                         const float a = sel8(r8, acc[rb0][h][0], acc[rb0][h][1], acc[rb0][h][2], acc[rb0][h][3],
                                              acc[rb0 + 1][h][0], acc[rb0 + 1][h][1], acc[rb0 + 1][h][2],
                                              acc[rb0 + 1][h][3]);
                         const float4 na = nr4[2 * hf], nb = nr4[2 * hf + 1];
                         const float xn = L2 ? sel8(r8, na.x, na.y, na.z, na.w, nb.x, nb.y, nb.z, nb.w) : 0.f;
-#else
-                        const float a = pk[((r8 >> 2) * 64 + lane) * 4 + (r8 & 3)];
-                        const float xn = L2 ? nrm[tr] : 0.f;
-#endif
                         float kv = L2 ? fmaf(-2.f, a, qn[h] + xn) : -a;
                         if constexpr (PACK) {
                             // L2: the clamp at 0 and the order map in two integer ops — a key
@@ -624,29 +643,6 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
             }
         }
         B16W_STAMP(2 * (t - t0) + 1);
-        // sibling lockstep (TileArgs::sync): publish this tile, wait (bounded) until the G
-        // workgroups of this row split have all finished it (minus the lag), so they enter the
-        // next tile together and its corpus stages are fetched from HBM once, then served from
-        // L2 to the other three.  Only lane 0 of wave 0 waits; the other waves run on into the
-        // next tile and stop at its first stage barrier.  A sibling that never shows up (not
-        // resident) turns the wait off for the rest of the launch.
-        if (sync_on && wave == 0 && t + 1 < t1) {
-            if (lane == 0) {
-                const uint32_t mine = (epoch << 16) + (uint32_t)(t - t0) + 1u;
-                __hip_atomic_store(sync + wgid, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t want = mine - (uint32_t)lag;
-                for (int spin = 0;; ++spin) {
-                    bool ok = true;
-#pragma unroll
-                    for (int s2 = 0; s2 < kG; ++s2)
-                        ok = ok && (int)(__hip_atomic_load(sync + sib0 + s2, __ATOMIC_RELAXED,
-                                                           __HIP_MEMORY_SCOPE_AGENT) - want) >= 0;
-                    if (ok) break;
-                    if (spin >= 4096) { sync_on = false; break; }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-            }
-        }
 #ifdef IMGREC_B16_STAMPS
         if (stamp_on && lane == 0) g_b16w_stamps[wave * 256 + 128 + (t - t0)] = (unsigned long long)nit;
         if (stamp_on && lane == 0 && t - t0 < 64) g_b16w_stamps[wave * 256 + 192 + (t - t0)] = ins_cyc;
@@ -716,8 +712,9 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
     }
 }
 
-hipError_t launch_b16_wide(const TileArgs& a, hipStream_t st) {
+hipError_t launch_b16_big(const TileArgs& a, hipStream_t st) {
     if (a.wr != 2 || a.wq != 4 || a.dp % kBKW != 0 || a.nsplit < 1) return hipErrorInvalidValue;
+    // the lane offsets are 32-bit: a tile's last group sits (kGPT - 1) * nsplit groups past its first
     if (((int64_t)(kGPT - 1) * a.nsplit * kRPP + kBQ) * a.dp * 4 + 8192 >= ((int64_t)1 << 32))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)(a.nqb * a.nsplit)), block(kNW * 64);
@@ -727,7 +724,7 @@ hipError_t launch_b16_wide(const TileArgs& a, hipStream_t st) {
 #define IMGREC_LAUNCH_B16W(KMV, L2V, PK)                                                             \
     hipLaunchKernelGGL((knn_b16w_tile_kernel<KMV, L2V, PK>), grid, block, 0, st, xh, a.xnorm,      \
                        a.nrows, a.dp, qh, a.qnorm, a.nq, a.nsplit, a.nqb, a.id_offset, a.cand_d,   \
-                       a.cand_i, a.ncand, a.ib, a.sync, a.epoch, a.sync_lag, a.sbound)
+                       a.cand_i, a.ncand, a.ib, a.sbound)
 #define IMGREC_LAUNCH_B16W_K(KMV, PK)                                                               \
     do { if (a.metric == 1) IMGREC_LAUNCH_B16W(KMV, 1, PK); else IMGREC_LAUNCH_B16W(KMV, 0, PK); } while (0)
     if (a.km == 8) {

@@ -27,8 +27,8 @@ thread_local std::string g_err;
 }  // namespace
 
 // The A/B and test knobs read at index creation (IMGREC_CUS, IMGREC_I8_WGPCU, IMGREC_MERGE_FUSE,
-// IMGREC_CHANCE_SKIP, IMGREC_B16W_SYNC_LAG, IMGREC_B16W_SHARED_BOUND; INTEGRATION.md "A/B
-// switches"): not product settings.
+// IMGREC_CHANCE_SKIP, IMGREC_B16W_SHARED_BOUND; INTEGRATION.md "A/B switches"): not product
+// settings.
 // An inherited one silently re-plans every launch, so the first read of each that is set says so
 // once on stderr.
 const char* test_knob(const char* name) {
@@ -319,7 +319,7 @@ void free_single(knn_index* ix) {
     for (void* p : {(void*)ix->xh, (void*)ix->xr, (void*)ix->xr_max, (void*)ix->qb16,
                     (void*)ix->q_resid, (void*)ix->floor, (void*)ix->mws_d, (void*)ix->mws_i,
                     (void*)ix->mws_f, (void*)ix->stat, (void*)ix->fb_cd, (void*)ix->fb_ci,
-                    (void*)ix->b16_sync, (void*)ix->sbound,
+                    (void*)ix->sbound,
                     (void*)ix->tail_ctl, (void*)ix->chance, (void*)ix->sc_key, (void*)ix->sc_lab,
                     (void*)ix->sc_meta, (void*)ix->sc_done, (void*)ix->heads, (void*)ix->i8_dyn})
         if (p) (void)hipFree(p);
@@ -713,10 +713,8 @@ int knn_plan_kernel(const knn_index_t* cix, int64_t nq, int k, char* name, int c
                       (ix->nblk8 + 15) / 16);
     } else if (use_b16(ix, cn, k)) {
         const Plan p = make_b16_plan(ix->ntotal, cn, k, ix->cus, ix->dpb);
-        if (p.big && IMGREC_B16_MFMA16)
+        if (p.big)
             std::snprintf(name, cap, "knn_b16w_tile_kernel<%d, %d, %s>", p.km, l2, p.ib > 0 ? "true" : "false");
-        else if (p.big)
-            std::snprintf(name, cap, "knn_b16_tile_kernel<%d, %d>", p.km, l2);
         else
             std::snprintf(name, cap, "knn_tile_topk_kernel<%d, %d, ..., %d, ...>", p.wr, p.wq, kModeBF16);
     } else if (use_split(ix, cn, k)) {

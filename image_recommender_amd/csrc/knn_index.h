@@ -67,7 +67,7 @@ int grow(T** p, size_t* cap, size_t need) {
 struct Plan {
     int wr, wq, km, bm, bq;
     int nqb, nq_pad, ntiles, nsplit, ncand, wgs;
-    bool big;                    // bf16 path: the 256 x 256-tile kernel (knn_b16.hip)
+    bool big;                    // bf16 path: the 256 x 256-tile kernel (knn_b16w.hip)
     int ib;                      // > 0: its packed-list form with ib split-local index bits
 };
 constexpr int64_t kQueryChunk = 8192;
@@ -192,8 +192,6 @@ struct knn_index {
     float* mws_d = nullptr; size_t mws_d_cap = 0;          // two-level candidate merge workspace
     int64_t* mws_i = nullptr; size_t mws_i_cap = 0;
     float* mws_f = nullptr; size_t mws_f_cap = 0;
-    uint32_t* b16_sync = nullptr; size_t b16_sync_cap = 0;   // 256 x 256 kernel sibling progress
-    uint32_t b16_epoch = 0;
     uint32_t* sbound = nullptr; size_t sbound_cap = 0;       // shared screen bound records (kSBWords per query)
     size_t xr_max_cap = 0;
     // exact re-run workspace (device-planned: queries, candidate lists, plan)

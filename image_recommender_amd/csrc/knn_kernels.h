@@ -32,12 +32,6 @@ struct TileArgs {
     int64_t* cand_i;            // nq x ncand labels
     int ncand;
     int ib = 0;                 // 256 x 256 bf16 kernel: > 0 = packed lists with ib index bits
-    // 256 x 256 bf16 kernel, optional: per-workgroup tile progress (one uint32 per workgroup,
-    // values (epoch << 16) + tiles done), so the query-block workgroups that share a row split
-    // start every tile together and read its corpus stages from L2 once (NULL = off)
-    uint32_t* sync = nullptr;
-    uint32_t epoch = 0;
-    int sync_lag = 0;           // tiles a workgroup may run ahead of its slowest sibling
     // 256 x 256 bf16 kernel, optional: the shared screen bound's per-query records (nq_pad x
     // kSBWords, reset by the query prep: SharedBoundPrep); NULL = every list screens alone
     uint32_t* sbound = nullptr;
@@ -206,27 +200,18 @@ constexpr int kSplitBK = IMGREC_SPLIT_BK, kSplitNS = IMGREC_SPLIT_NS, kSplitWB =
 constexpr int kB16WR = IMGREC_B16_WR, kB16WQ = IMGREC_B16_WQ, kB16WB = IMGREC_B16_WB;
 constexpr int kB16NS = IMGREC_B16_NS, kB16WGPCU = IMGREC_B16_WGPCU, kB16Pad = 64;
 
-// 256 x 256-tile bf16 kernel (knn_b16.hip): one 8-wave workgroup per CU, k <= 10, batches of at
+// 256 x 256-tile bf16 kernel (knn_b16w.hip): one 8-wave workgroup per CU, k <= 10, batches of at
 // least kB16BigMinQ queries.
 #ifndef IMGREC_B16_BIG_MINQ
 #define IMGREC_B16_BIG_MINQ 512
 #endif
-#ifndef IMGREC_B16_MFMA16
-#define IMGREC_B16_MFMA16 1
-#endif
-// packed candidate lists (knn_b16w.hip) while a split's row index fits this many bits: the
+// packed candidate lists while a split's row index fits this many bits: the
 // approximate keys keep 23 - ib mantissa bits (relative truncation <= 2^(ib - 23))
 #ifndef IMGREC_B16_PACK_MAXIB
 #define IMGREC_B16_PACK_MAXIB 14
 #endif
 constexpr int kB16PackMaxIB = IMGREC_B16_PACK_MAXIB;
 constexpr int kB16BigRows = 256, kB16BigQueries = 256, kB16BigMinQ = IMGREC_B16_BIG_MINQ;
-// The shared screen bound's LDS image takes the place of knn_b16w.hip's insertion park (round 6's
-// A/B switch, off by default): a build with the park, or on the 32 x 32 kernel, has no bound.
-#ifndef IMGREC_B16W_NOPARK
-#define IMGREC_B16W_NOPARK 1
-#endif
-constexpr bool kSharedBoundBuilt = IMGREC_B16_MFMA16 != 0 && IMGREC_B16W_NOPARK != 0;
 
 // Small-batch candidate pass on the block-scaled int8 copy (knn_i8.hip): per (query, row split)
 // the km best approximate keys, nq <= 8 queries in one launch, nsplit workgroups.
@@ -292,8 +277,7 @@ hipError_t launch_i8_query_prep(const float* src, int64_t n, int d, int dp, int6
 hipError_t launch_rows_ingest(const float* src, int64_t n, int d, int dp, int64_t n_pad,
                               int normalize, float* dst, float* norms, hipStream_t st);
 hipError_t launch_tile_topk(const TileArgs& a, hipStream_t st);
-hipError_t launch_b16_big(const TileArgs& a, hipStream_t st);     // knn_b16.hip
-hipError_t launch_b16_wide(const TileArgs& a, hipStream_t st);    // knn_b16w.hip (16x16x32 form)
+hipError_t launch_b16_big(const TileArgs& a, hipStream_t st);     // knn_b16w.hip
 hipError_t launch_merge(const float* cd, const int64_t* ci, int64_t nq, int nlists, int kin,
                         int64_t stride_q, int64_t stride_l, int k, int metric, int negate_in,
                         float* D, int64_t* I, hipStream_t st);

@@ -21,6 +21,9 @@ namespace imgrec {
 
 namespace {
 
+// 1 = L2, 0 = inner product (cosine rows are normalised): the kernels' metric argument
+int kmetric_of(const knn_index* ix) { return ix->metric == KNN_METRIC_L2 ? 1 : 0; }
+
 // Timing events around the dominant (fused) kernel launch of a chunk.
 int timed_begin(knn_index* ix, hipStream_t st, hipEvent_t* e1) {
     *e1 = nullptr;
@@ -41,7 +44,7 @@ int timed_begin(knn_index* ix, hipStream_t st, hipEvent_t* e1) {
 // Exact fp32 path over nq padded queries (qpad holds make_plan(nq).nq_pad zero-padded rows).
 int exact_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,
                 int64_t* I, hipStream_t st, bool timed) {
-    const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    const int kmetric = kmetric_of(ix);
     int rc;
     if (stream_lists_ok(ix, nq)) {
         // <= 4 queries: the corpus streamed once (HBM-bound) into exact lists of 32 per row
@@ -177,7 +180,7 @@ int certify_chunk(knn_index* ix, RerankArgs& r, const float* qpad, const float* 
     t.dp = ix->dp;
     t.nrows = (int)ix->ntotal;
     t.ntiles = (int)((ix->ntotal + bm - 1) / bm);
-    t.metric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    t.metric = kmetric_of(ix);
     t.xb = ix->xb;
     t.xn = ix->xn;
     t.id_offset = ix->id_offset;
@@ -227,25 +230,65 @@ bool fuse_merge_single(const knn_index* ix, int nlists, int km) {
     return ix->merge_single && nlists <= 64 && km <= 16;
 }
 
-// Sibling lockstep of the 256 x 256 bf16 kernel (TileArgs::sync): IMGREC_B16W_SYNC_LAG = the
-// tiles a workgroup may run ahead of the slowest workgroup of its row split; unset or negative =
-// off.
-int b16_sync_lag() {
-    static const int v = [] {
-        const char* e = test_knob("IMGREC_B16W_SYNC_LAG");
-        return e && *e ? std::atoi(e) : -1;
-    }();
-    return v;
+// A candidate chunk's buffers: the per-split lists (nq x ncand), the merged K' = kc candidates
+// and, for the chains that merge with launch_merge_candidates, the merge floor.
+int grow_cand(knn_index* ix, int64_t nq, int ncand, int kc, bool floor) {
+    int rc;
+    if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)nq * ncand)) != KNN_OK) return rc;
+    if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)nq * ncand)) != KNN_OK) return rc;
+    if ((rc = grow(&ix->cand2_d, &ix->cand2_d_cap, (size_t)nq * kc)) != KNN_OK) return rc;
+    if ((rc = grow(&ix->cand2_i, &ix->cand2_i_cap, (size_t)nq * kc)) != KNN_OK) return rc;
+    return floor ? grow(&ix->floor, &ix->floor_cap, (size_t)nq) : KNN_OK;
 }
 
-// The shared screen bound of a chunk that runs the 256 x 256 16x16-MFMA kernel (knn_b16w.hip): grows
+// The RerankArgs fields every candidate chain sets alike.  The caller adds its arithmetic's bound
+// (c_split, c_trunc, q_resid, xr_max), the merged candidates and the raw per-split lists.
+RerankArgs rerank_args(const knn_index* ix, int mode, const float* qpad, const float* qnorm,
+                       int64_t nq, int k, int kc, float* D, int64_t* I) {
+    RerankArgs r{};
+    r.mode = mode;
+    r.qp = qpad; r.qnorm = qnorm; r.dp = ix->dp; r.xb = ix->xb; r.xn = ix->xn;
+    r.xn_max = ix->xn_max; r.id_offset = ix->id_offset; r.kc = kc; r.nq = nq; r.k = k;
+    r.metric = kmetric_of(ix); r.c_fp = rerank_coef(ix->dp); r.D = D; r.I = I;
+    return r;
+}
+
+// The chunk's nlists per-split lists of km (ix->cand_d / cand_i, query stride ncand) become the
+// rerank's r->kc candidates and their floor: merged by the rerank itself — in one level (`single`:
+// fuse_merge_single) or in two (fuse_merge_level1) — or by a merge launch, whose second level the
+// rerank may take (fuse_merge_level2).
+int merge_for_rerank(knn_index* ix, int64_t nq, int nlists, int km, int ncand, bool single,
+                     RerankArgs* r, hipStream_t st) {
+    const int kc = r->kc, ngrp = (nlists + 63) / 64;
+    int rc;
+    if (ngrp > 1) {
+        if ((rc = grow(&ix->mws_d, &ix->mws_d_cap, (size_t)nq * ngrp * kc)) != KNN_OK) return rc;
+        if ((rc = grow(&ix->mws_i, &ix->mws_i_cap, (size_t)nq * ngrp * kc)) != KNN_OK) return rc;
+        if ((rc = grow(&ix->mws_f, &ix->mws_f_cap, (size_t)nq * ngrp)) != KNN_OK) return rc;
+    }
+    int l1G = 0;
+    const bool l0 = !single && fuse_merge_level1(ix, nq, nlists, km);
+    if (l0) l1G = ngrp;
+    else if (!single)
+        KNN_HIP(launch_merge_candidates(ix->cand_d, ix->cand_i, nq, nlists, km, ncand, km, kc,
+                                        ix->id_offset, ix->cand2_d, ix->cand2_i, ix->floor,
+                                        ix->mws_d, ix->mws_i, ix->mws_f, st,
+                                        fuse_merge_level2(ix, nq) ? &l1G : nullptr));
+    r->cd = ix->cand2_d; r->ci = ix->cand2_i; r->floor = ix->floor;
+    if (single) r->s_lists = nlists;
+    if (l1G > 0) { r->l1_d = ix->mws_d; r->l1_i = ix->mws_i; r->l1_floor = ix->mws_f; r->l1_G = l1G; }
+    if (l0) r->l0_lists = nlists;
+    return KNN_OK;
+}
+
+// The shared screen bound of a chunk that runs the 256 x 256 kernel (knn_b16w.hip): grows
 // the index's per-query records and fills what the query prep kernel needs to reset them (sb->rec
 // stays NULL for every other plan, and with IMGREC_B16W_SHARED_BOUND=0).  The prep reads the corpus
 // maxima, so they are refreshed here, ahead of it.
 int shared_bound_prep(knn_index* ix, const Plan& p, const float* qnorm, hipStream_t st,
                       SharedBoundPrep* sb) {
     *sb = SharedBoundPrep{};
-    if (!ix->shared_bound || !p.big || !kSharedBoundBuilt) return KNN_OK;
+    if (!ix->shared_bound || !p.big) return KNN_OK;
     int rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
     if ((rc = grow(&ix->sbound, &ix->sbound_cap, (size_t)p.nq_pad * kSBWords)) != KNN_OK) return rc;
@@ -256,7 +299,7 @@ int shared_bound_prep(knn_index* ix, const Plan& p, const float* qnorm, hipStrea
     sb->c_acc = b16_acc_coef(ix->dpb);
     sb->c_fp = rerank_coef(ix->dp);
     sb->c_trunc = p.ib > 0 ? (float)std::ldexp(1.0, p.ib - 23) : 0.f;
-    sb->metric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    sb->metric = kmetric_of(ix);
     sb->km = p.km;
     return KNN_OK;
 }
@@ -264,7 +307,7 @@ int shared_bound_prep(knn_index* ix, const Plan& p, const float* qnorm, hipStrea
 // bf16 candidates (one bf16 MFMA per product) + exact fp32 rerank of K' = 64 + certificate.
 int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,
               int64_t* I, hipStream_t st, bool timed, bool q_ready, bool first) {
-    const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    const int kmetric = kmetric_of(ix);
     const int kc = kB16Cand;
     const Plan p = make_b16_plan(ix->ntotal, nq, k, ix->cus, ix->dpb);
     const int km = p.km;
@@ -272,11 +315,7 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
     if ((rc = grow(&ix->qb16, &ix->qb16_cap, (size_t)p.nq_pad * ix->dpb)) != KNN_OK) return rc;
     if ((rc = grow(&ix->q_resid, &ix->q_resid_cap, (size_t)p.nq_pad)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)nq * p.ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)nq * p.ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand2_d, &ix->cand2_d_cap, (size_t)nq * kc)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand2_i, &ix->cand2_i_cap, (size_t)nq * kc)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->floor, &ix->floor_cap, (size_t)nq)) != KNN_OK) return rc;
+    if ((rc = grow_cand(ix, nq, p.ncand, kc, true)) != KNN_OK) return rc;
     if ((rc = grow_stats(ix, nq, st)) != KNN_OK) return rc;
     // (the prep — here or search_locked's — also resets the shared screen bound's records)
     SharedBoundPrep sb;
@@ -291,49 +330,19 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     a.id_offset = ix->id_offset; a.cand_d = ix->cand_d; a.cand_i = ix->cand_i; a.ncand = p.ncand;
     a.ib = p.big ? p.ib : 0;
     a.sbound = sb.rec;
-    if (p.big && b16_sync_lag() >= 0) {
-        // sibling lockstep of the 256 x 256 kernel: progress slots zeroed once, a new epoch per
-        // launch (values of earlier launches compare as "not yet")
-        const size_t cap0 = ix->b16_sync_cap;
-        if ((rc = grow(&ix->b16_sync, &ix->b16_sync_cap, (size_t)p.wgs)) != KNN_OK) return rc;
-        if (ix->b16_sync_cap != cap0)
-            KNN_HIP(hipMemsetAsync(ix->b16_sync, 0, ix->b16_sync_cap * sizeof(uint32_t), st));
-        ix->b16_epoch = (ix->b16_epoch + 1) & 0xffffu;
-        a.sync = ix->b16_sync;
-        a.epoch = ix->b16_epoch;
-        a.sync_lag = b16_sync_lag();
-    }
     hipEvent_t e1 = nullptr;
     if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
     KNN_HIP(p.big ? launch_b16_big(a, st) : launch_tile_topk(a, st));
     if (e1) KNN_HIP(hipEventRecord(e1, st));
-    const int nlists = p.ncand / km, ngrp = (nlists + 63) / 64;
-    if (ngrp > 1) {
-        if ((rc = grow(&ix->mws_d, &ix->mws_d_cap, (size_t)nq * ngrp * kc)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->mws_i, &ix->mws_i_cap, (size_t)nq * ngrp * kc)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->mws_f, &ix->mws_f_cap, (size_t)nq * ngrp)) != KNN_OK) return rc;
-    }
-    int l1G = 0;
-    const bool single = fuse_merge_single(ix, nlists, km);
-    const bool l0 = !single && fuse_merge_level1(ix, nq, nlists, km);
-    if (l0) l1G = (nlists + 63) / 64;
-    else if (!single)
-        KNN_HIP(launch_merge_candidates(ix->cand_d, ix->cand_i, nq, nlists, km, p.ncand, km, kc,
-                                        ix->id_offset, ix->cand2_d, ix->cand2_i, ix->floor,
-                                        ix->mws_d, ix->mws_i, ix->mws_f, st,
-                                        fuse_merge_level2(ix, nq) ? &l1G : nullptr));
-    RerankArgs r{};
-    r.mode = kModeBF16;
-    if (single) r.s_lists = nlists;
-    r.qp = qpad; r.qnorm = qnorm; r.dp = ix->dp; r.xb = ix->xb; r.xn = ix->xn;
-    r.xn_max = ix->xn_max; r.id_offset = ix->id_offset; r.cd = ix->cand2_d; r.ci = ix->cand2_i;
-    r.kc = kc; r.nq = nq; r.k = k; r.metric = kmetric; r.c_split = b16_acc_coef(ix->dpb);
-    r.c_fp = rerank_coef(ix->dp); r.D = D; r.I = I;
+    const int nlists = p.ncand / km;
+    RerankArgs r = rerank_args(ix, kModeBF16, qpad, qnorm, nq, k, kc, D, I);
+    r.c_split = b16_acc_coef(ix->dpb);
     r.c_trunc = a.ib > 0 ? (float)std::ldexp(1.0, a.ib - 23) : 0.f;
-    r.q_resid = ix->q_resid; r.xr_max = ix->xr_max; r.floor = ix->floor;
+    r.q_resid = ix->q_resid; r.xr_max = ix->xr_max;
     r.sbound = a.sbound;
-    if (l1G > 0) { r.l1_d = ix->mws_d; r.l1_i = ix->mws_i; r.l1_floor = ix->mws_f; r.l1_G = l1G; }
-    if (l0) r.l0_lists = nlists;
+    if ((rc = merge_for_rerank(ix, nq, nlists, km, p.ncand, fuse_merge_single(ix, nlists, km), &r,
+                               st)) != KNN_OK)
+        return rc;
     r.raw_d = ix->cand_d; r.raw_i = ix->cand_i; r.raw_lists = nlists; r.raw_km = km;
     r.raw_stride_q = p.ncand;
     return certify_chunk(ix, r, qpad, qnorm, nq, k, D, I, st, first);
@@ -343,7 +352,7 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
 // rerank of K' = 64 + certificate: the bf16 path's chain with the int8 copy's bound.
 int i8_chunk(knn_index* ix, const float* qraw, const float* qpad, const float* qnorm, int64_t nq,
              int k, float* D, int64_t* I, hipStream_t st, bool timed, bool first) {
-    const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    const int kmetric = kmetric_of(ix);
     const int kc = kB16Cand;
     const Plan p = make_i8_plan(ix->ntotal, nq, k, ix->cus, ix->i8_wgpcu, ix->nblk8);
     // direct: no merge, no rerank launch — the certificate tail reranks every query's list entries
@@ -359,11 +368,7 @@ int i8_chunk(knn_index* ix, const float* qraw, const float* qpad, const float* q
     int rc;
     if ((rc = ensure_i8(ix, st)) != KNN_OK) return rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)nq * ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)nq * ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand2_d, &ix->cand2_d_cap, (size_t)nq * kc)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand2_i, &ix->cand2_i_cap, (size_t)nq * kc)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->floor, &ix->floor_cap, (size_t)nq)) != KNN_OK) return rc;
+    if ((rc = grow_cand(ix, nq, ncand, kc, true)) != KNN_OK) return rc;
     if ((rc = grow_stats(ix, nq, st)) != KNN_OK) return rc;
     // qraw non-NULL: the scan quantises the raw query rows itself and writes qpad / qnorm /
     // q8r (I8Args::qsrc); otherwise the codes ix->q8 / q8s / q8r came with qpad from
@@ -405,65 +410,34 @@ int i8_chunk(knn_index* ix, const float* qraw, const float* qpad, const float* q
     if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
     KNN_HIP(launch_i8_scan(a, st));
     if (e1) KNN_HIP(hipEventRecord(e1, st));
-    const int nlists = p.nsplit, ngrp = (nlists + 63) / 64;
+    const int nlists = p.nsplit;
+    RerankArgs r = rerank_args(ix, kModeI8, qpad, qnorm, nq, k, kc, D, I);
+    r.c_split = i8_acc_coef(ix->nblk8);
+    r.q_resid = ix->q8r; r.xr_max = ix->x8r_max;
+    r.raw_d = ix->cand_d; r.raw_i = ix->cand_i; r.raw_lists = raw ? 16 * nlists : nlists;
+    r.raw_km = p.km;
+    r.raw_stride_q = ncand;
     if (direct) {
-        RerankArgs r{};
-        r.mode = kModeI8;
-        r.qp = qpad; r.qnorm = qnorm; r.dp = ix->dp; r.xb = ix->xb; r.xn = ix->xn;
-        r.xn_max = ix->xn_max; r.id_offset = ix->id_offset;
-        r.kc = kc; r.nq = nq; r.k = k; r.metric = kmetric; r.c_split = i8_acc_coef(ix->nblk8);
-        r.c_fp = rerank_coef(ix->dp); r.D = D; r.I = I;
-        r.q_resid = ix->q8r; r.xr_max = ix->x8r_max;
-        r.raw_d = ix->cand_d; r.raw_i = ix->cand_i; r.raw_lists = raw ? 16 * nlists : nlists;
-        r.raw_km = p.km;
-        r.raw_stride_q = ncand;
         r.direct = 1;
         r.heads = ix->heads;
         r.heads_n = nlists;
-        return certify_chunk(ix, r, qpad, qnorm, nq, k, D, I, st, first);
+    } else if ((rc = merge_for_rerank(ix, nq, nlists, p.km, ncand, false, &r, st)) != KNN_OK) {
+        return rc;
     }
-    if (ngrp > 1) {
-        if ((rc = grow(&ix->mws_d, &ix->mws_d_cap, (size_t)nq * ngrp * kc)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->mws_i, &ix->mws_i_cap, (size_t)nq * ngrp * kc)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->mws_f, &ix->mws_f_cap, (size_t)nq * ngrp)) != KNN_OK) return rc;
-    }
-    int l1G = 0;
-    const bool l0 = fuse_merge_level1(ix, nq, nlists, p.km);
-    if (l0) l1G = (nlists + 63) / 64;
-    else
-        KNN_HIP(launch_merge_candidates(ix->cand_d, ix->cand_i, nq, nlists, p.km, p.ncand, p.km, kc,
-                                        ix->id_offset, ix->cand2_d, ix->cand2_i, ix->floor,
-                                        ix->mws_d, ix->mws_i, ix->mws_f, st,
-                                        fuse_merge_level2(ix, nq) ? &l1G : nullptr));
-    RerankArgs r{};
-    r.mode = kModeI8;
-    r.qp = qpad; r.qnorm = qnorm; r.dp = ix->dp; r.xb = ix->xb; r.xn = ix->xn;
-    r.xn_max = ix->xn_max; r.id_offset = ix->id_offset; r.cd = ix->cand2_d; r.ci = ix->cand2_i;
-    r.kc = kc; r.nq = nq; r.k = k; r.metric = kmetric; r.c_split = i8_acc_coef(ix->nblk8);
-    r.c_fp = rerank_coef(ix->dp); r.D = D; r.I = I;
-    r.c_trunc = 0.f;
-    r.q_resid = ix->q8r; r.xr_max = ix->x8r_max; r.floor = ix->floor;
-    if (l1G > 0) { r.l1_d = ix->mws_d; r.l1_i = ix->mws_i; r.l1_floor = ix->mws_f; r.l1_G = l1G; }
-    if (l0) r.l0_lists = nlists;
-    r.raw_d = ix->cand_d; r.raw_i = ix->cand_i; r.raw_lists = nlists; r.raw_km = p.km;
-    r.raw_stride_q = p.ncand;
     return certify_chunk(ix, r, qpad, qnorm, nq, k, D, I, st, first);
 }
 
 // Split-bf16 candidates + exact rerank + certificate.
 int split_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,
                 int64_t* I, hipStream_t st, bool timed, bool first) {
-    const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    const int kmetric = kmetric_of(ix);
     const int kc = split_kc(k);
     const Plan p = make_split_plan(ix->ntotal, nq, kc, ix->cus);
     int rc;
     if ((rc = ensure_split(ix, st)) != KNN_OK) return rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
     if ((rc = grow(&ix->qsplit, &ix->qsplit_cap, (size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)nq * p.ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)nq * p.ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand2_d, &ix->cand2_d_cap, (size_t)nq * kc)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand2_i, &ix->cand2_i_cap, (size_t)nq * kc)) != KNN_OK) return rc;
+    if ((rc = grow_cand(ix, nq, p.ncand, kc, false)) != KNN_OK) return rc;   // (launch_merge: no floor)
     if ((rc = grow_stats(ix, nq, st)) != KNN_OK) return rc;
     KNN_HIP(launch_split_rows(qpad, p.nq_pad, ix->dp, kSplitBK, ix->qsplit, st));
     TileArgs a{};
@@ -481,12 +455,9 @@ int split_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
     // global top-K' approximate candidates, raw ascending keys (merge in its L2 convention)
     KNN_HIP(launch_merge(ix->cand_d, ix->cand_i, nq, p.ncand / kc, kc, p.ncand, kc, kc, 1, 0,
                          ix->cand2_d, ix->cand2_i, st));
-    RerankArgs r{};
-    r.mode = kModeSplit;
-    r.qp = qpad; r.qnorm = qnorm; r.dp = ix->dp; r.xb = ix->xb; r.xn = ix->xn;
-    r.xn_max = ix->xn_max; r.id_offset = ix->id_offset; r.cd = ix->cand2_d; r.ci = ix->cand2_i;
-    r.kc = kc; r.nq = nq; r.k = k; r.metric = kmetric; r.c_split = split_coef(ix->dp);
-    r.c_fp = rerank_coef(ix->dp); r.D = D; r.I = I;
+    RerankArgs r = rerank_args(ix, kModeSplit, qpad, qnorm, nq, k, kc, D, I);
+    r.cd = ix->cand2_d; r.ci = ix->cand2_i;
+    r.c_split = split_coef(ix->dp);
     r.raw_d = ix->cand_d; r.raw_i = ix->cand_i; r.raw_lists = p.ncand / kc; r.raw_km = kc;
     r.raw_stride_q = p.ncand;
     return certify_chunk(ix, r, qpad, qnorm, nq, k, D, I, st, first);
@@ -546,7 +517,7 @@ bool use_split(const knn_index* ix, int64_t nq, int k) {
 int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                   hipStream_t st) {
     const int normalize = ix->metric == KNN_METRIC_COSINE;
-    const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    const int kmetric = kmetric_of(ix);
     ix->last_split_queries = 0;
     ix->stat_valid = false;
     if (k > KNN_MAX_K) {               // register top-k lists end at 32: faiss's GEMM + select form

@@ -209,7 +209,7 @@ def test_bf16_mode_rejected_for_tiny_d(faiss):
     (2061, 128, 777, 9, "ip"),        # ragged last group (2061 = 257 x 8 + 5), partial tiles
 ])
 def test_bf16_big_tile_kernel(faiss, n, d, nq, k, metric):
-    """Batches of >= 512 queries with k <= 10 run the 256 x 256-tile kernel (knn_b16.hip)."""
+    """Batches of >= 512 queries with k <= 10 run the 256 x 256-tile kernel (knn_b16w.hip)."""
     if d == 1968:
         xb = concat_rows(n, seed=n)
         xq = xb[:nq] + np.float32(0.01)

@@ -46,6 +46,13 @@ SIGNATURES = {
     "knn_reconstruct_n": (_i, [_vp, _i64, _i64, _vp]),
     "knn_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "knn_search_device": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "knn_range_search": (_i, [_vp, _vp, _i64, _f, C.POINTER(_vp)]),
+    "knn_range_search_device": (_i, [_vp, _vp, _i64, _f, _vp, C.POINTER(_vp)]),
+    "knn_range_nq": (_i64, [_vp]),
+    "knn_range_size": (_i64, [_vp]),
+    "knn_range_copy": (_i, [_vp, _vp, _vp, _vp]),
+    "knn_range_device": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "knn_range_free": (_i, [_vp]),
     "knn_merge_device": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "knn_packed_bytes": (_i64, [_i64, _i]),
     "knn_merge_packed_device": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _vp]),

@@ -298,6 +298,12 @@ int create_single(int d, int metric, int device, knn_index** out) {
     if (const char* e = test_knob("IMGREC_MERGE_SINGLE")) ix->merge_single = *e != '0';
     if (const char* e = test_knob("IMGREC_STREAM_LISTS")) ix->stream_lists = *e != '0';
     if (const char* e = test_knob("IMGREC_B16W_SHARED_BOUND")) ix->shared_bound = *e != '0';
+    // IMGREC_RANGE_CAP=<entries> (tests): the range search's initial append capacity, so small
+    // shapes reach the overflow re-run
+    if (const char* e = test_knob("IMGREC_RANGE_CAP")) {
+        const long long v = std::atoll(e);
+        if (v > 0) ix->range_cap0 = (size_t)v;
+    }
     if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ix->fence, hipEventDisableTiming) != hipSuccess) {
         if (ix->stream) (void)hipStreamDestroy(ix->stream);
@@ -330,6 +336,7 @@ void free_single(knn_index* ix) {
         if (p) (void)hipFree(p);
     largek_free(ix);
     hugek_free(ix);
+    range_free(ix);
     for (hipEvent_t e : ix->ev) (void)hipEventDestroy(e);
     if (ix->fence) (void)hipEventDestroy(ix->fence);
     (void)hipStreamDestroy(ix->stream);
@@ -536,6 +543,76 @@ int knn_search(knn_index_t* ix, const float* q, int64_t nq, int k, float* D, int
         std::memcpy(D, ix->pd, (size_t)nq * k * sizeof(float));
         std::memcpy(I, ix->pi, (size_t)nq * k * sizeof(int64_t));
     }
+    return KNN_OK;
+}
+
+static int range_args_ok(knn_index_t* ix, const float* q, int64_t nq, float radius,
+                         knn_range_result_t** out) {
+    if (out) *out = nullptr;
+    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
+    if (!out) KNN_FAIL(KNN_EINVAL, "out is NULL");
+    if (nq < 0 || (nq > 0 && !q)) KNN_FAIL(KNN_EINVAL, "bad query pointer (nq=%lld)", (long long)nq);
+    if (radius != radius) KNN_FAIL(KNN_EINVAL, "radius is NaN");
+    return KNN_OK;
+}
+
+int knn_range_search_device(knn_index_t* ix, const float* q, int64_t nq, float radius, void* stream,
+                            knn_range_result_t** out) {
+    int rc;
+    if ((rc = range_args_ok(ix, q, nq, radius, out)) != KNN_OK) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    if (ix->multi) return multi_range_search(ix, q, false, nq, radius, st, out);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
+    if ((rc = range_search_locked(ix, q, nq, radius, st, out)) != KNN_OK) return rc;
+    return fence_end(ix, st);
+}
+
+int knn_range_search(knn_index_t* ix, const float* q, int64_t nq, float radius,
+                     knn_range_result_t** out) {
+    int rc;
+    if ((rc = range_args_ok(ix, q, nq, radius, out)) != KNN_OK) return rc;
+    if (ix->multi) return multi_range_search(ix, q, true, nq, radius, nullptr, out);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
+    if (nq > 0) {
+        if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)nq * ix->d)) != KNN_OK) return rc;
+        KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice,
+                               ix->stream));
+    }
+    if ((rc = range_search_locked(ix, ix->hq, nq, radius, ix->stream, out)) != KNN_OK) return rc;
+    KNN_HIP(hipStreamSynchronize(ix->stream));
+    return fence_end_synced(ix);
+}
+
+int64_t knn_range_nq(const knn_range_result_t* r) { return r ? r->nq : KNN_EINVAL; }
+int64_t knn_range_size(const knn_range_result_t* r) { return r ? r->size : KNN_EINVAL; }
+
+int knn_range_copy(const knn_range_result_t* r, int64_t* lims, float* D, int64_t* I) {
+    if (!r) KNN_FAIL(KNN_EINVAL, "result is NULL");
+    DeviceGuard g(r->device);
+    KNN_HIP(hipEventSynchronize(r->done));
+    if (lims) KNN_HIP(hipMemcpy(lims, r->lims, (size_t)(r->nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (D && r->size > 0) KNN_HIP(hipMemcpy(D, r->D, (size_t)r->size * sizeof(float), hipMemcpyDeviceToHost));
+    if (I && r->size > 0) KNN_HIP(hipMemcpy(I, r->I, (size_t)r->size * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return KNN_OK;
+}
+
+int knn_range_device(const knn_range_result_t* r, const int64_t** lims, const float** D,
+                     const int64_t** I) {
+    if (!r) KNN_FAIL(KNN_EINVAL, "result is NULL");
+    DeviceGuard g(r->device);
+    KNN_HIP(hipEventSynchronize(r->done));
+    if (lims) *lims = r->lims;
+    if (D) *D = r->D;
+    if (I) *I = r->I;
+    return KNN_OK;
+}
+
+int knn_range_free(knn_range_result_t* r) {
+    range_result_free(r);
     return KNN_OK;
 }
 

@@ -1,7 +1,8 @@
 // knn_index.h — internal state of one k-NN index and the helpers the C-ABI translation units
 // share (knn_capi.cpp: entry points; knn_plan.cpp: launch geometry and error-bound coefficients;
 // knn_search.cpp: the search paths; knn_io.cpp: the faiss file layout; knn_multi.cpp: one index
-// over several devices).  Not part of the public ABI (include/imgrec_knn.h).
+// over several devices; knn_range.hip: range search).  Not part of the public ABI
+// (include/imgrec_knn.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -223,6 +224,29 @@ struct knn_index {
     uint64_t* hk_b = nullptr; size_t hk_b_cap = 0;
     unsigned* hk_off = nullptr; size_t hk_off_cap = 0;
     void* hk_tmp = nullptr; size_t hk_tmp_cap = 0;
+    // range search (knn_range.hip): the append buffer (entries + their queries; starts at
+    // range_cap0 entries, IMGREC_RANGE_CAP, and grows to a chunk's total when that overflows it),
+    // the entries scattered into query segments, per-query counts, segment offsets, scatter
+    // cursors, and the chunk's total on the device and in page-locked host memory
+    size_t range_cap0 = size_t(1) << 20;
+    uint64_t* rg_ent = nullptr; size_t rg_ent_cap = 0;
+    uint32_t* rg_entq = nullptr; size_t rg_entq_cap = 0;
+    uint64_t* rg_seg = nullptr; size_t rg_seg_cap = 0;
+    uint32_t* rg_cnt = nullptr; size_t rg_cnt_cap = 0;
+    uint32_t* rg_off = nullptr; size_t rg_off_cap = 0;
+    uint32_t* rg_cur = nullptr; size_t rg_cur_cap = 0;
+    unsigned long long* rg_total = nullptr; size_t rg_total_cap = 0;
+    unsigned long long* rg_total_h = nullptr;
+};
+
+// One range search's result (knn_range_search): buffers on `device`, complete once `done` fires.
+struct knn_range_result {
+    int device = 0;
+    int64_t nq = 0, size = 0;
+    int64_t* lims = nullptr;     // nq + 1
+    float* D = nullptr;          // size (one unused element when empty)
+    int64_t* I = nullptr;
+    hipEvent_t done = nullptr;
 };
 
 namespace imgrec {
@@ -243,6 +267,9 @@ void free_single(knn_index* ix);
 // knn_search.cpp
 int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                   hipStream_t st);
+// knn_set_timing: records the first event of a pair on st and returns the second in *e1 (to be
+// recorded after the timed launch); *e1 = NULL while timing is off
+int timed_begin(knn_index* ix, hipStream_t st, hipEvent_t* e1);
 int read_search_stats(knn_index* ix, int64_t* split_q, int64_t* fallback_q, int64_t* first_fail,
                       float* ratio);
 bool use_b16(const knn_index* ix, int64_t nq, int k);
@@ -277,5 +304,14 @@ hipError_t launch_merge_huge(const float* cD, const int64_t* cI, int nlists, int
 hipError_t launch_merge_any(const float* cD, const int64_t* cI, int nlists, int64_t nq, int kin,
                             int64_t sd, int64_t si, int k, int metric, float* D, int64_t* I,
                             hipStream_t st);
+// knn_range.hip: every row within `radius` of each of the nq device queries on `st` (waits once
+// per query chunk for the chunk's size); labels are row + id_offset
+int range_search_locked(knn_index* ix, const float* q, int64_t nq, float radius, hipStream_t st,
+                        knn_range_result** out);
+// a result on `device` from host arrays (the multi-device merge); waits for the upload
+int range_result_from_host(int device, int64_t nq, const int64_t* lims, const float* D, const int64_t* I,
+                           hipStream_t st, knn_range_result** out);
+void range_result_free(knn_range_result* r);
+void range_free(knn_index* ix);
 
 }  // namespace imgrec

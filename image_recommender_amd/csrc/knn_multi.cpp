@@ -16,6 +16,8 @@
 // the torchrun path (sharded.py), with device-to-device copies instead of an RCCL all-gather.
 #include <cstdlib>
 #include <cstring>
+#include <thread>
+#include <utility>
 
 #include "knn_multi.h"
 
@@ -358,6 +360,117 @@ int multi_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int
                            ix->stream));
     KNN_HIP(hipStreamSynchronize(ix->stream));
     return fence_end_synced(ix);
+}
+
+// Range search: every shard runs the single-device range search on its own device and stream, one
+// host thread each (a shard's search waits for its own result size), maps its labels and copies
+// its result to the host; the segments of a query (each already in (key, label) order, labels
+// disjoint) are merged there and the merged result is uploaded to the first device.  A pair's key
+// does not depend on the shard it sits in, so the result equals the single-device one bit for bit.
+int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq, float radius,
+                       hipStream_t st, knn_range_result** out) {
+    knn_multi* m = M(ix);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    const int ndev = (int)m->shards.size();
+    if (q_on_host) st = ix->stream;
+    int rc;
+    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
+    if (q_on_host && nq > 0) {
+        if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)nq * ix->d)) != KNN_OK) return rc;
+        KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
+        q = ix->hq;
+    }
+    KNN_HIP(hipEventRecord(m->ready, st));
+    struct ShardHits {
+        std::vector<int64_t> lims;
+        std::vector<float> D;
+        std::vector<int64_t> I;
+        int rc = KNN_OK;
+        std::string err;
+    };
+    std::vector<ShardHits> hits(ndev);
+    auto run_shard = [&](int s) -> int {
+        knn_index* sh = m->shards[s];
+        ShardHits& h = hits[s];
+        const bool local = sh->device == ix->device && !m->force_remote;
+        DeviceGuard gs(sh->device);
+        std::lock_guard<std::mutex> lks(sh->mu);
+        const hipStream_t ss = sh->stream;
+        int r;
+        KNN_HIP(hipStreamWaitEvent(ss, m->ready, 0));
+        if ((r = fence_begin(sh, ss)) != KNN_OK) return r;
+        const float* qs = q;
+        if (!local && nq > 0) {
+            if ((r = grow(&m->sq[s], &m->sq_cap[s], (size_t)nq * ix->d)) != KNN_OK) return r;
+            KNN_HIP(hipMemcpyPeerAsync(m->sq[s], sh->device, q, ix->device,
+                                       (size_t)nq * ix->d * sizeof(float), ss));
+            qs = m->sq[s];
+        }
+        knn_range_result* res = nullptr;
+        if ((r = range_search_locked(sh, qs, nq, radius, ss, &res)) != KNN_OK) return r;
+        const int64_t n = res->size;
+        h.lims.resize((size_t)nq + 1);
+        h.D.resize((size_t)n);
+        h.I.resize((size_t)n);
+        hipError_t e = hipSuccess;
+        if (n > 0) e = launch_map_labels(res->I, n, m->lmap[s], ix->id_offset, ss);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(h.lims.data(), res->lims, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ss);
+        if (e == hipSuccess && n > 0)
+            e = hipMemcpyAsync(h.D.data(), res->D, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ss);
+        if (e == hipSuccess && n > 0)
+            e = hipMemcpyAsync(h.I.data(), res->I, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, ss);
+        const hipError_t e2 = hipStreamSynchronize(ss);
+        range_result_free(res);
+        if (e != hipSuccess || e2 != hipSuccess)
+            KNN_FAIL(KNN_EHIP, "range search shard %d: %s", s, hipGetErrorString(e != hipSuccess ? e : e2));
+        return fence_end_synced(sh);
+    };
+    {
+        std::vector<std::thread> th;
+        for (int s = 0; s < ndev; ++s)
+            th.emplace_back([&, s]() {
+                hits[s].rc = run_shard(s);
+                if (hits[s].rc != KNN_OK) hits[s].err = last_error();   // the message is per thread
+            });
+        for (std::thread& t : th) t.join();
+    }
+    for (int s = 0; s < ndev; ++s)
+        if (hits[s].rc != KNN_OK) KNN_FAIL(hits[s].rc, "%s", hits[s].err.c_str());
+    // per query: the shards' sorted segments into one (key, label) order
+    const bool l2 = ix->metric == KNN_METRIC_L2;
+    std::vector<int64_t> lims((size_t)nq + 1, 0);
+    for (int64_t i = 0; i < nq; ++i) {
+        int64_t c = 0;
+        for (int s = 0; s < ndev; ++s) c += hits[s].lims[i + 1] - hits[s].lims[i];
+        lims[i + 1] = lims[i] + c;
+    }
+    std::vector<float> D((size_t)lims[nq]);
+    std::vector<int64_t> I((size_t)lims[nq]);
+    // the device sort's key: the order-preserving bits of the key (wave_ops.h key_bits_ordered)
+    auto key_bits = [](float k) {
+        uint32_t u;
+        std::memcpy(&u, &k, sizeof u);
+        return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    };
+    std::vector<std::pair<std::pair<uint32_t, int64_t>, float>> seg;
+    for (int64_t i = 0; i < nq; ++i) {
+        seg.clear();
+        for (int s = 0; s < ndev; ++s)
+            for (int64_t e = hits[s].lims[i]; e < hits[s].lims[i + 1]; ++e) {
+                const float d = hits[s].D[e];
+                seg.push_back({{key_bits(l2 ? d : -d), hits[s].I[e]}, d});
+            }
+        std::sort(seg.begin(), seg.end());
+        for (size_t e = 0; e < seg.size(); ++e) {
+            D[(size_t)lims[i] + e] = seg[e].second;
+            I[(size_t)lims[i] + e] = seg[e].first.second;
+        }
+    }
+    if ((rc = range_result_from_host(ix->device, nq, lims.data(), D.data(), I.data(), st, out)) != KNN_OK)
+        return rc;
+    return q_on_host ? fence_end_synced(ix) : fence_end(ix, st);
 }
 
 int multi_set_metric(knn_index* ix, int metric) {

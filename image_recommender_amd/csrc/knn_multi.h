@@ -18,6 +18,10 @@ int multi_reconstruct_n(knn_index* ix, int64_t i0, int64_t n, float* x);
 int multi_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I);
 int multi_search_device(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                         hipStream_t st);
+// range search over every shard concurrently, merged per query on the host into the (key, label)
+// order; q on the host (q_on_host; `st` unused) or on the first device, ready on `st`
+int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq, float radius,
+                       hipStream_t st, knn_range_result** out);
 int multi_set_metric(knn_index* ix, int metric);
 int multi_set_trained(knn_index* ix, bool trained);
 int multi_set_timing(knn_index* ix, int enable);

@@ -1,0 +1,591 @@
+// knn_range.hip — range search (faiss Index::range_search): every stored row within a radius of
+// each query, in one pass over the corpus that writes only what passes.
+//
+// Pipeline of one query chunk (range_search_locked):
+//   1. knn_range_tile_kernel: the exact fp32 contraction of knn_kernels.hip's tile kernel
+//      (v_mfma_f32_32x32x2_f32, LDS-DMA ring) with its own stage loop; the epilogue forms the key
+//      ((|q|^2 + |x|^2) - 2 q.x clamped at 0, or -q.x), tests `key < r` (r = -radius for IP) and
+//      appends the survivors to a buffer: per 32-row block a wave counts its lanes' survivors,
+//      reserves their slots with ONE returning agent-scope atomic and every lane stores its
+//      (key bits << 32 | row, query) entries with plain stores.  Per-query hit counts are kept in
+//      a register over the whole row split and added once per lane pair at the end.
+//   2. range_scan_kernel: exclusive scan of the counts -> segment offsets and `lims`.
+//   3. the chunk's total reaches the host (the one wait): the result is allocated; a total past
+//      the append buffer's capacity grows the buffer and runs step 1 again (the counts and the
+//      total were complete; the entries were not).
+//   4. range_scatter_kernel: entries into their query's segment (one atomic per run of
+//      consecutive entries of one query).
+//   5. sort_u64_segments (knn_hugek.hip): every segment into (key, row) order.
+//   6. range_unpack_kernel: D (IP sign restored) and I (row + id_offset).
+//
+// Arithmetic: a pair's key depends on (q, x, d, metric) only.  The depth order of the MFMA chain
+// is fixed by the stage depth, which is chosen from the row stride alone (32 when it divides, 16
+// otherwise); the two geometries (256 rows x 32 queries for batches of <= 32, 128 x 128 beyond)
+// share it: an MFMA output element depends on its own row and column only.  So results are
+// bitwise independent of N, the batch, the append capacity and the sharding.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "knn_index.h"
+#include "lds_dma.h"
+#include "wave_ops.h"
+
+namespace imgrec {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// The tile geometry of knn_kernels.hip (TileGeom) without the top-k epilogue's key parking:
+// WR x WQ waves of 128 rows x 32 queries, BK-deep stages in an NS ring.
+template <int WR, int WQ, int NS, int BK>
+struct RangeGeom {
+    static constexpr int WB = 4;
+    static constexpr int NW = WR * WQ, NT = NW * 64;
+    static constexpr int RW = 32 * WB;
+    static constexpr int BM = WR * RW, BQ = WQ * 32;
+    static constexpr int CPR = BK / 4;                 // 16-B chunks per staged row
+    static constexpr int RPP = 64 / CPR;               // rows per 1-KiB DMA piece
+    static constexpr int RPB = 64 / BK;                // rows per 256-B bank row
+    static constexpr int SA = BM * BK, SB = BQ * BK, STAGE = SA + SB;   // floats
+    static constexpr int PA = BM / RPP, PB = BQ / RPP, PIECES = PA + PB;
+    static constexpr int LPW = PIECES / NW;
+    static constexpr int LDS_FLOATS = NS * STAGE + NS * BM;
+    static_assert(BK == 16 || BK == 32, "stage depth");
+    static_assert(PIECES % NW == 0, "pieces must divide evenly over waves");
+    static_assert(BM % 64 == 0, "norm DMA uses whole waves");
+    static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
+};
+
+__device__ __forceinline__ void dma16(const float* g, uint32_t lds) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
+}
+
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+
+struct RangeArgs {
+    const float* xb;            // corpus, rows padded to 256, stride dp
+    const float* xnorm;
+    uint32_t nrows;
+    int dp;
+    const float* qp;            // nqb x BQ padded queries
+    const float* qnorm;
+    int nq, metric;             // metric 1 = L2, otherwise inner product
+    float r;                    // a pair passes when key < r
+    int ntiles, nsplit, nqb;
+    uint64_t* ent;              // append buffer: key bits << 32 | row ...
+    uint32_t* entq;             // ... and the chunk-local query of each entry
+    unsigned long long cap;     // entries the buffer holds
+    unsigned long long* total;  // survivors of the chunk (counted past cap as well)
+    uint32_t* counts;           // per query
+};
+
+template <int WR, int WQ, int NS, int BK>
+__global__ void __launch_bounds__(WR * WQ * 64, WR * WQ == 4 ? 2 : 1)
+knn_range_tile_kernel(const RangeArgs a) {
+    using G = RangeGeom<WR, WQ, NS, BK>;
+    constexpr int WB = G::WB, RW = G::RW;
+    constexpr int NW = G::NW, BM = G::BM, BQ = G::BQ, SA = G::SA, STAGE = G::STAGE;
+    constexpr int PA = G::PA, LPW = G::LPW, CPR = G::CPR, RPP = G::RPP, RPB = G::RPB;
+    constexpr int KH = BK / 2;
+    __shared__ __attribute__((aligned(16))) float smem[G::LDS_FLOATS];
+    // XCD-aware block -> (query block, row split) map of the exact kernel: the workgroups of one
+    // XCD share row splits, so the corpus stages they stream come from that XCD's L2
+    const int nwg = gridDim.x, wg = blockIdx.x;
+    const int xcd = wg & 7, qq = nwg >> 3, rr8 = nwg & 7;
+    const int wgid = (xcd < rr8 ? xcd * (qq + 1) : rr8 * (qq + 1) + (xcd - rr8) * qq) + (wg >> 3);
+    const int nqb = a.nqb, nsplit = a.nsplit, dp = a.dp;
+    if (wgid >= nqb * nsplit) return;
+    float* const norm_base = smem + NS * STAGE;
+    const int qb = wgid % nqb;
+    const int split = wgid / nqb;
+    const int t1 = split < a.ntiles ? (a.ntiles - split + nsplit - 1) / nsplit : 0;
+    auto tile = [&](int j) { return split + j * nsplit; };
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave / WQ;
+    const int wq = wave % WQ;
+    const int li = lane & 31;
+    const int lh = lane >> 5;
+    const int qcol = qb * BQ + wq * 32 + li;     // < nq_pad
+    const bool qvalid = qcol < a.nq;
+    const int metric = a.metric;
+    const float rad = a.r;
+    float qn = (metric == 1) ? a.qnorm[qcol] : 0.f;
+    asm volatile("" : "+v"(qn));
+
+    const int prow = lane / CPR, pchk = lane % CPR;
+    const int goff0 = prow * dp + 4 * (pchk ^ (((0 * RPP + prow) / RPB) % CPR));
+    const int goff1 = prow * dp + 4 * (pchk ^ (((1 * RPP + prow) / RPB) % CPR));
+    const int fsw = (li / RPB) % CPR;
+    int fo[CPR / 2];
+#pragma unroll
+    for (int c = 0; c < CPR / 2; ++c) fo[c] = li * BK + 4 * ((lh * (CPR / 2) + c) ^ fsw);
+
+    const int nsteps = dp / BK;
+    const float* qbase = a.qp + (size_t)qb * BQ * dp;
+
+    int64_t poff[LPW];
+    bool pis_a[LPW];
+    uint32_t pdst[LPW];
+#pragma unroll
+    for (int j = 0; j < LPW; ++j) {
+        const int pc = wave * LPW + j;
+        pis_a[j] = pc < PA;
+        const int prow0 = pis_a[j] ? pc * RPP : (pc - PA) * RPP;
+        poff[j] = (int64_t)prow0 * dp + (((prow0 / RPP) & 1) ? goff1 : goff0);
+        pdst[j] = (uint32_t)(pis_a[j] ? pc * 256 : SA + (pc - PA) * 256) * 4u;
+    }
+    const uint32_t smem_u32 = lds_u32(smem);
+    const uint32_t norm_u32 = lds_u32(norm_base);
+    int it = 0, is = 0, ibuf = 0;
+    const float* itile = a.xb + (size_t)tile(0) * BM * dp;
+    auto issue_next = [&]() __attribute__((always_inline)) {
+        if (it >= t1) return;
+        const uint32_t st = smem_u32 + (uint32_t)(ibuf * STAGE) * 4u;
+        if (is == 0) {
+            for (int j = wave; j < BM / 64; j += NW)
+                dma4_norm(a.xnorm + (size_t)tile(it) * BM + j * 64 + lane,
+                          norm_u32 + (uint32_t)((it % NS) * BM + j * 64) * 4u);
+        }
+        const int k0 = is * BK;
+#pragma unroll
+        for (int j = 0; j < LPW; ++j) dma16((pis_a[j] ? itile : qbase) + poff[j] + k0, st + pdst[j]);
+        if (++is == nsteps) { is = 0; ++it; itile += (size_t)nsplit * BM * dp; }
+        ibuf = (ibuf + 1 == NS) ? 0 : ibuf + 1;
+    };
+
+#pragma unroll
+    for (int j = 0; j < NS - 1; ++j) issue_next();
+    int remaining = t1 * nsteps;
+    int cbuf = 0;
+    int nhits = 0;                               // this lane's survivors over the whole split
+
+    for (int t = 0; t < t1; ++t) {
+        const uint32_t row0 = (uint32_t)tile(t) * BM;
+        f32x16 acc[WB];
+#pragma unroll
+        for (int b = 0; b < WB; ++b) acc[b] = (f32x16){0.f};
+
+        for (int s = 0; s < nsteps; ++s) {
+            --remaining;
+            if (remaining >= NS - 2) wait_vmcnt<LPW * (NS - 2)>();
+            else wait_vmcnt<0>();
+            barrier_lds();                       // everyone's DMA landed; previous stage read
+
+            const float* st = smem + cbuf * STAGE;
+            cbuf = (cbuf + 1 == NS) ? 0 : cbuf + 1;
+            float av[WB][KH], bq[KH];
+            {
+                const float* bp = st + SA + wq * 32 * BK;
+#pragma unroll
+                for (int c = 0; c < CPR / 2; ++c) {
+                    const float4 v = *reinterpret_cast<const float4*>(bp + fo[c]);
+                    bq[4 * c] = v.x; bq[4 * c + 1] = v.y; bq[4 * c + 2] = v.z; bq[4 * c + 3] = v.w;
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < WB; ++b) {
+                const float* ap = st + (wr * RW + b * 32) * BK;
+#pragma unroll
+                for (int c = 0; c < CPR / 2; ++c) {
+                    const float4 v = *reinterpret_cast<const float4*>(ap + fo[c]);
+                    av[b][4 * c] = v.x; av[b][4 * c + 1] = v.y; av[b][4 * c + 2] = v.z; av[b][4 * c + 3] = v.w;
+                }
+            }
+            issue_next();                        // refills the buffer the previous stage used
+#pragma unroll
+            for (int kk = 0; kk < KH; ++kk) {
+#pragma unroll
+                for (int b = 0; b < WB; ++b)
+                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[b][kk], bq[kk], acc[b], 0, 0, 0);
+            }
+        }
+
+        // ---- epilogue: threshold and append.  The tile's norms landed before its first stage's
+        // barrier; their ring slot is rewritten NS tiles later, behind a barrier every wave
+        // reaches only after this epilogue.
+        const float* nrm = norm_base + (t % NS) * BM;
+#pragma unroll
+        for (int b = 0; b < WB; ++b) {
+            float key[16];
+            unsigned mask = 0;
+            const int rb = wr * RW + b * 32 + 4 * lh;          // row of accumulator reg 0
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                      // regs 4j..4j+3 = rows rb+8j+0..3
+                float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (metric == 1) n4 = *reinterpret_cast<const float4*>(nrm + rb + 8 * j);
+                const float nv[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int r = 4 * j + i;
+                    const float ip = acc[b][r];
+                    float kv;
+                    if (metric == 1) {
+                        kv = fmaf(-2.f, ip, qn + nv[i]);
+                        kv = kv < 0.f ? 0.f : kv;
+                    } else {
+                        kv = -ip;
+                    }
+                    key[r] = kv;
+                    // a NaN key fails the comparison: never returned
+                    const bool pass = qvalid && (row0 + (uint32_t)(rb + 8 * j + i) < a.nrows) && kv < rad;
+                    mask |= (unsigned)pass << r;
+                }
+            }
+            if (__any(mask != 0)) {                            // wave-uniform: all lanes inside
+                const int cnt = __popc(mask);
+                const int ex = wave_excl_scan_i32(cnt);
+                const int tot = wave_sum_i32(cnt);
+                unsigned long long base = 0;
+                if (lane == 0)
+                    base = __hip_atomic_fetch_add(a.total, (unsigned long long)tot, __ATOMIC_RELAXED,
+                                                  __HIP_MEMORY_SCOPE_AGENT);
+                const uint32_t blo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+                const uint32_t bhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32));
+                unsigned long long slot = (((unsigned long long)bhi << 32) | blo) + (unsigned)ex;
+                nhits += cnt;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if ((mask >> r) & 1u) {
+                        if (slot < a.cap) {
+                            const uint32_t row = row0 + (uint32_t)(rb + (r & 3) + 8 * (r >> 2));
+                            a.ent[slot] = ((uint64_t)key_bits_ordered(key[r]) << 32) | row;
+                            a.entq[slot] = (uint32_t)qcol;
+                        }
+                        ++slot;
+                    }
+                }
+            }
+        }
+    }
+
+    // the two lanes of a query (its rows' halves) add their count once
+    const int both = nhits + __shfl_xor(nhits, 32, 64);
+    if (lh == 0 && qvalid && both > 0)
+        __hip_atomic_fetch_add(a.counts + qcol, (uint32_t)both, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Exclusive scan of a chunk's counts (nqc <= kQueryChunk): off[i] and cur[i] = the start of query
+// i's segment (i <= nqc: off[nqc] = the total), lims[i] = base + off[i].  One 256-thread workgroup.
+__global__ void __launch_bounds__(256)
+range_scan_kernel(const uint32_t* __restrict__ counts, int nqc, int64_t base, uint32_t* __restrict__ off,
+                  uint32_t* __restrict__ cur, int64_t* __restrict__ lims) {
+    __shared__ uint32_t part[256];
+    __shared__ uint32_t tot;
+    const int t = threadIdx.x;
+    const int per = (nqc + 255) / 256;
+    const int i0 = t * per, i1 = min(nqc, i0 + per);
+    uint32_t s = 0;
+    for (int i = i0; i < i1; ++i) s += counts[i];
+    part[t] = s;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t run = 0;
+        for (int j = 0; j < 256; ++j) { const uint32_t v = part[j]; part[j] = run; run += v; }
+        tot = run;
+    }
+    __syncthreads();
+    uint32_t run = part[t];
+    for (int i = i0; i < i1; ++i) {
+        off[i] = run; cur[i] = run; lims[i] = base + (int64_t)run;
+        run += counts[i];
+    }
+    if (t == 0) { off[nqc] = tot; cur[nqc] = tot; lims[nqc] = base + (int64_t)tot; }
+}
+
+// Entry e of the append buffer -> its query's segment.  A run of consecutive entries of one query
+// inside a wave (a lane's survivors of a block are consecutive) takes one atomic for the run.
+__global__ void __launch_bounds__(256)
+range_scatter_kernel(const uint64_t* __restrict__ ent, const uint32_t* __restrict__ entq, int64_t total,
+                     uint32_t* __restrict__ cur, uint64_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = e < total;
+    const uint32_t q = valid ? entq[e] : 0xffffffffu;
+    const uint64_t v = valid ? ent[e] : 0;
+    const uint32_t qprev = (uint32_t)__shfl_up((int)q, 1, 64);
+    const bool head = valid && (lane == 0 || qprev != q);
+    const uint64_t heads = __ballot(head);
+    const int nvalid = __popcll(__ballot(valid));              // valid lanes are a prefix
+    // this lane's run: from the last head at or below it to the next head (or the valid end)
+    const uint64_t below = heads & (lane == 63 ? ~0ull : ((2ull << lane) - 1));
+    const int h = below ? 63 - __builtin_clzll(below) : 0;
+    const uint64_t above = h == 63 ? 0ull : heads >> (h + 1);
+    const int next = above ? h + 1 + __builtin_ctzll(above) : nvalid;
+    uint32_t base = 0;
+    if (head) base = __hip_atomic_fetch_add(cur + q, (uint32_t)(next - h), __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT);
+    base = (uint32_t)__shfl((int)base, h, 64);
+    if (valid) out[(size_t)base + (uint32_t)(lane - h)] = v;
+}
+
+__global__ void __launch_bounds__(256)
+range_unpack_kernel(const uint64_t* __restrict__ sorted, int64_t total, int metric, int64_t id_offset,
+                    float* __restrict__ D, int64_t* __restrict__ I) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const uint64_t x = sorted[e];
+    const float key = key_from_ordered((uint32_t)(x >> 32));
+    D[e] = metric == 1 ? key : -key;
+    I[e] = (int64_t)(uint32_t)x + id_offset;
+}
+
+struct RangePlan { int wr, wq, bk, bm, bq, nqb, nq_pad, ntiles, nsplit; };
+
+// One geometry per batch size, one stage depth per row stride (the depth order of the keys).
+RangePlan make_range_plan(int64_t ntotal, int64_t nq, int dp, int cus) {
+    RangePlan p{};
+    if (nq <= 32) { p.wr = 2; p.wq = 1; } else { p.wr = 1; p.wq = 4; }
+    p.bk = dp % 32 == 0 ? 32 : 16;
+    p.bm = p.wr * 128;
+    p.bq = p.wq * 32;
+    p.nqb = (int)((nq + p.bq - 1) / p.bq);
+    p.nq_pad = p.nqb * p.bq;
+    p.ntiles = (int)((ntotal + p.bm - 1) / p.bm);
+    const int target = cus * 2;
+    p.nsplit = std::max(1, std::min((target + p.nqb - 1) / p.nqb, p.ntiles));
+    return p;
+}
+
+hipError_t launch_range_tile(const RangePlan& p, const RangeArgs& a, hipStream_t st) {
+    const dim3 grid((unsigned)(p.nqb * p.nsplit));
+#define IMGREC_RANGE_LAUNCH(WRV, WQV, NSV, BKV)                                                   \
+    hipLaunchKernelGGL((knn_range_tile_kernel<WRV, WQV, NSV, BKV>), grid, dim3(WRV * WQV * 64), 0, st, a)
+    // 2-slot rings at 32-deep stages: 74 / 66 KiB of LDS, so two workgroups share a CU (a 3-slot
+    // ring of the 256 x 32 tile leaves one 2-wave workgroup, half the SIMDs, per CU)
+    if (p.wr == 2 && p.bk == 32) IMGREC_RANGE_LAUNCH(2, 1, 2, 32);
+    else if (p.wr == 2) IMGREC_RANGE_LAUNCH(2, 1, 3, 16);
+    else if (p.bk == 32) IMGREC_RANGE_LAUNCH(1, 4, 2, 32);
+    else IMGREC_RANGE_LAUNCH(1, 4, 2, 16);
+#undef IMGREC_RANGE_LAUNCH
+    return hipGetLastError();
+}
+
+int new_result(int device, int64_t nq, knn_range_result** out) {
+    knn_range_result* r = new knn_range_result();
+    r->device = device;
+    r->nq = nq;
+    *out = r;
+    KNN_HIP(hipEventCreateWithFlags(&r->done, hipEventDisableTiming));
+    KNN_HIP(hipMalloc((void**)&r->lims, (size_t)(nq + 1) * sizeof(int64_t)));
+    return KNN_OK;
+}
+
+// D / I of `n` entries (never NULL: an empty result keeps one unused element)
+int alloc_hits(int64_t n, float** D, int64_t** I) {
+    KNN_HIP(hipMalloc((void**)D, (size_t)std::max<int64_t>(n, 1) * sizeof(float)));
+    KNN_HIP(hipMalloc((void**)I, (size_t)std::max<int64_t>(n, 1) * sizeof(int64_t)));
+    return KNN_OK;
+}
+
+struct ChunkHits { float* D = nullptr; int64_t* I = nullptr; int64_t n = 0; };
+
+int range_chunks(knn_index* ix, const float* q, int64_t nq, float radius, hipStream_t st,
+                 knn_range_result* res, std::vector<ChunkHits>& chunks) {
+    const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    const int normalize = ix->metric == KNN_METRIC_COSINE;
+    int rc;
+    if (!ix->rg_total_h) KNN_HIP(hipHostMalloc((void**)&ix->rg_total_h, sizeof(unsigned long long), hipHostMallocDefault));
+    if ((rc = grow(&ix->rg_total, &ix->rg_total_cap, (size_t)1)) != KNN_OK) return rc;
+    int64_t base = 0;
+    for (int64_t c0 = 0; c0 < nq; c0 += kQueryChunk) {
+        const int64_t cn = std::min(kQueryChunk, nq - c0);
+        const RangePlan p = make_range_plan(ix->ntotal, cn, ix->dp, ix->cus);
+        if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
+        if ((rc = grow(&ix->qnorm, &ix->qnorm_cap, (size_t)p.nq_pad)) != KNN_OK) return rc;
+        if ((rc = grow(&ix->rg_cnt, &ix->rg_cnt_cap, (size_t)cn)) != KNN_OK) return rc;
+        if ((rc = grow(&ix->rg_off, &ix->rg_off_cap, (size_t)cn + 1)) != KNN_OK) return rc;
+        if ((rc = grow(&ix->rg_cur, &ix->rg_cur_cap, (size_t)cn + 1)) != KNN_OK) return rc;
+        if ((rc = grow(&ix->rg_ent, &ix->rg_ent_cap, ix->range_cap0)) != KNN_OK) return rc;
+        if ((rc = grow(&ix->rg_entq, &ix->rg_entq_cap, ix->range_cap0)) != KNN_OK) return rc;
+        KNN_HIP(launch_rows_ingest(q + c0 * ix->d, cn, ix->d, ix->dp, p.nq_pad, normalize, ix->qpad,
+                                   ix->qnorm, st));
+        RangeArgs a{};
+        a.xb = ix->xb; a.xnorm = ix->xn; a.nrows = (uint32_t)ix->ntotal; a.dp = ix->dp;
+        a.qp = ix->qpad; a.qnorm = ix->qnorm; a.nq = (int)cn; a.metric = kmetric;
+        a.r = kmetric ? radius : -radius;
+        a.ntiles = p.ntiles; a.nsplit = p.nsplit; a.nqb = p.nqb;
+        a.total = ix->rg_total; a.counts = ix->rg_cnt;
+        auto pass = [&]() -> int {
+            a.ent = ix->rg_ent; a.entq = ix->rg_entq;
+            a.cap = (unsigned long long)std::min(ix->rg_ent_cap, ix->rg_entq_cap);
+            KNN_HIP(hipMemsetAsync(ix->rg_total, 0, sizeof(unsigned long long), st));
+            KNN_HIP(hipMemsetAsync(ix->rg_cnt, 0, (size_t)cn * sizeof(uint32_t), st));
+            hipEvent_t e1 = nullptr;              // knn_set_timing: the tile kernel's own time
+            int rc2;
+            if ((rc2 = timed_begin(ix, st, &e1)) != KNN_OK) return rc2;
+            KNN_HIP(launch_range_tile(p, a, st));
+            if (e1) KNN_HIP(hipEventRecord(e1, st));
+            hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(256), 0, st, ix->rg_cnt, (int)cn, base,
+                               ix->rg_off, ix->rg_cur, res->lims + c0);
+            KNN_HIP(hipGetLastError());
+            return KNN_OK;
+        };
+        if ((rc = pass()) != KNN_OK) return rc;
+        KNN_HIP(hipMemcpyAsync(ix->rg_total_h, ix->rg_total, sizeof(unsigned long long),
+                               hipMemcpyDeviceToHost, st));
+        KNN_HIP(hipStreamSynchronize(st));
+        const unsigned long long total = *ix->rg_total_h;
+        if (total > (unsigned long long)UINT32_MAX)
+            KNN_FAIL(KNN_EINVAL, "range search: %llu hits in one chunk of %lld queries (limit 2^32 - 1): "
+                     "lower the radius or split the batch", total, (long long)cn);
+        ChunkHits h;
+        h.n = (int64_t)total;
+        chunks.push_back(h);
+        if ((rc = alloc_hits(h.n, &chunks.back().D, &chunks.back().I)) != KNN_OK) return rc;
+        if (total > 0) {
+            if (total > a.cap) {
+                // the counts were complete, the entries were not: the same pass with room for all
+                if ((rc = grow(&ix->rg_ent, &ix->rg_ent_cap, (size_t)total)) != KNN_OK) return rc;
+                if ((rc = grow(&ix->rg_entq, &ix->rg_entq_cap, (size_t)total)) != KNN_OK) return rc;
+                if ((rc = pass()) != KNN_OK) return rc;
+            }
+            if ((rc = grow(&ix->rg_seg, &ix->rg_seg_cap, (size_t)total)) != KNN_OK) return rc;
+            const unsigned blocks = (unsigned)((total + 255) / 256);
+            hipLaunchKernelGGL(range_scatter_kernel, dim3(blocks), dim3(256), 0, st, ix->rg_ent, ix->rg_entq,
+                               (int64_t)total, ix->rg_cur, ix->rg_seg);
+            KNN_HIP(hipGetLastError());
+            // sorted segments land back in the append buffer (its capacity covers the total)
+            KNN_HIP(sort_u64_segments(ix->rg_seg, ix->rg_ent, (int64_t)total, (int)cn, ix->rg_off, 64u,
+                                      &ix->hk_tmp, &ix->hk_tmp_cap, false, st));
+            hipLaunchKernelGGL(range_unpack_kernel, dim3(blocks), dim3(256), 0, st, ix->rg_ent, (int64_t)total,
+                               kmetric, ix->id_offset, chunks.back().D, chunks.back().I);
+            KNN_HIP(hipGetLastError());
+        }
+        base += (int64_t)total;
+    }
+    return KNN_OK;
+}
+
+void free_chunks(std::vector<ChunkHits>& chunks) {
+    for (ChunkHits& c : chunks) {
+        if (c.D) (void)hipFree(c.D);
+        if (c.I) (void)hipFree(c.I);
+    }
+    chunks.clear();
+}
+
+}  // namespace
+
+int range_search_locked(knn_index* ix, const float* q, int64_t nq, float radius, hipStream_t st,
+                        knn_range_result** out) {
+    *out = nullptr;
+    if (ix->ntotal > (int64_t)UINT32_MAX)
+        KNN_FAIL(KNN_EINVAL, "range search: %lld rows in one shard (limit 2^32 - 1): split the index "
+                 "over more shards", (long long)ix->ntotal);
+    knn_range_result* res = nullptr;
+    int rc = new_result(ix->device, nq, &res);
+    std::vector<ChunkHits> chunks;
+    const bool l2 = ix->metric == KNN_METRIC_L2;
+    if (rc == KNN_OK) {
+        if (ix->ntotal == 0 || nq == 0 || (l2 && radius <= 0.f)) {
+            const hipError_t e = hipMemsetAsync(res->lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st);
+            if (e != hipSuccess) { set_err("hipMemsetAsync failed: %s", hipGetErrorString(e)); rc = KNN_EHIP; }
+        } else {
+            rc = range_chunks(ix, q, nq, radius, st, res, chunks);
+        }
+    }
+    if (rc == KNN_OK) {
+        int64_t size = 0;
+        for (const ChunkHits& c : chunks) size += c.n;
+        res->size = size;
+        if (chunks.size() == 1) {
+            res->D = chunks[0].D;
+            res->I = chunks[0].I;
+            chunks.clear();
+        } else if ((rc = alloc_hits(size, &res->D, &res->I)) == KNN_OK) {
+            int64_t at = 0;
+            for (const ChunkHits& c : chunks) {
+                if (c.n == 0) continue;
+                hipError_t e = hipMemcpyAsync(res->D + at, c.D, (size_t)c.n * sizeof(float), hipMemcpyDeviceToDevice, st);
+                if (e == hipSuccess)
+                    e = hipMemcpyAsync(res->I + at, c.I, (size_t)c.n * sizeof(int64_t), hipMemcpyDeviceToDevice, st);
+                if (e != hipSuccess) { set_err("hipMemcpyAsync failed: %s", hipGetErrorString(e)); rc = KNN_EHIP; break; }
+                at += c.n;
+            }
+            if (rc == KNN_OK && !chunks.empty() && hipStreamSynchronize(st) != hipSuccess) {
+                set_err("hipStreamSynchronize failed");
+                rc = KNN_EHIP;
+            }
+        }
+    }
+    if (rc == KNN_OK && hipEventRecord(res->done, st) != hipSuccess) {
+        set_err("hipEventRecord failed");
+        rc = KNN_EHIP;
+    }
+    free_chunks(chunks);
+    if (rc != KNN_OK) {
+        (void)hipStreamSynchronize(st);          // nothing in flight may still write the buffers
+        range_result_free(res);
+        return rc;
+    }
+    *out = res;
+    return KNN_OK;
+}
+
+int range_result_from_host(int device, int64_t nq, const int64_t* lims, const float* D, const int64_t* I,
+                           hipStream_t st, knn_range_result** out) {
+    *out = nullptr;
+    knn_range_result* res = nullptr;
+    int rc = new_result(device, nq, &res);
+    const int64_t size = lims[nq];
+    if (rc == KNN_OK) rc = alloc_hits(size, &res->D, &res->I);
+    if (rc == KNN_OK) {
+        res->size = size;
+        hipError_t e = hipMemcpyAsync(res->lims, lims, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && size > 0)
+            e = hipMemcpyAsync(res->D, D, (size_t)size * sizeof(float), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && size > 0)
+            e = hipMemcpyAsync(res->I, I, (size_t)size * sizeof(int64_t), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);     // the host arrays are the caller's
+        if (e == hipSuccess) e = hipEventRecord(res->done, st);
+        if (e != hipSuccess) { set_err("range result upload failed: %s", hipGetErrorString(e)); rc = KNN_EHIP; }
+    }
+    if (rc != KNN_OK) {
+        range_result_free(res);
+        return rc;
+    }
+    *out = res;
+    return KNN_OK;
+}
+
+void range_result_free(knn_range_result* r) {
+    if (!r) return;
+    DeviceGuard g(r->device);
+    if (r->done) {
+        (void)hipEventSynchronize(r->done);
+        (void)hipEventDestroy(r->done);
+    }
+    for (void* p : {(void*)r->lims, (void*)r->D, (void*)r->I})
+        if (p) (void)hipFree(p);
+    delete r;
+}
+
+void range_free(knn_index* ix) {
+    for (void* p : {(void*)ix->rg_ent, (void*)ix->rg_entq, (void*)ix->rg_seg, (void*)ix->rg_cnt,
+                    (void*)ix->rg_off, (void*)ix->rg_cur, (void*)ix->rg_total})
+        if (p) (void)hipFree(p);
+    if (ix->rg_total_h) (void)hipHostFree(ix->rg_total_h);
+    ix->rg_ent = ix->rg_seg = nullptr;
+    ix->rg_entq = ix->rg_cnt = ix->rg_off = ix->rg_cur = nullptr;
+    ix->rg_total = ix->rg_total_h = nullptr;
+    ix->rg_ent_cap = ix->rg_entq_cap = ix->rg_seg_cap = ix->rg_cnt_cap = ix->rg_off_cap = ix->rg_cur_cap = 0;
+    ix->rg_total_cap = 0;
+}
+
+}  // namespace imgrec

@@ -24,6 +24,8 @@ namespace {
 // 1 = L2, 0 = inner product (cosine rows are normalised): the kernels' metric argument
 int kmetric_of(const knn_index* ix) { return ix->metric == KNN_METRIC_L2 ? 1 : 0; }
 
+}  // namespace
+
 // Timing events around the dominant (fused) kernel launch of a chunk.
 int timed_begin(knn_index* ix, hipStream_t st, hipEvent_t* e1) {
     *e1 = nullptr;
@@ -40,6 +42,8 @@ int timed_begin(knn_index* ix, hipStream_t st, hipEvent_t* e1) {
     ix->ev_used += 2;
     return KNN_OK;
 }
+
+namespace {
 
 // Exact fp32 path over nq padded queries (qpad holds make_plan(nq).nq_pad zero-padded rows).
 int exact_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,

@@ -19,6 +19,10 @@ reference call                    where
 ``index.search(q, k)``            main/search_from_image.py:247, Analytics/rt_Search.py:63
 ================================  =================================================================
 
+Beyond the reference's own calls, ``index.range_search(x, thresh) -> (lims, D, I)`` (every faiss
+flat index has it: all rows within a radius, the near-duplicate query) is served by every class
+here, multi-device indexes included; ``sharded.ShardedIndex`` and ``ivfpq`` do not have it.
+
 Semantics: every index class here is an EXACT flat index (the north_star parity target is
 ``IndexFlatL2``).  ``IndexHNSWFlat`` and ``IndexIVFPQ`` keep their constructor signatures and
 attributes (``hnsw.efSearch``, ``nprobe``, ``nlist``, ...) so the reference code runs unchanged,
@@ -80,6 +84,41 @@ def _device_list(device: int, devices):
     if not devices:
         raise ValueError("devices must list at least one device")
     return devices
+
+
+class RangeResult:
+    """A range search's device-resident result (include/imgrec_knn.h knn_range_result_t): owns the
+    handle and frees it when dropped."""
+
+    def __init__(self, handle: C.c_void_p):
+        self._h = handle
+        lib = _lib.load()
+        self.nq = int(lib.knn_range_nq(handle))
+        self.size = int(lib.knn_range_size(handle))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        lib = getattr(_lib, "_lib", None) if _lib is not None else None
+        if h is not None and lib is not None:
+            lib.knn_range_free(h)
+            self._h = None
+
+    def device_ptrs(self):
+        """(lims, D, I) device addresses: int64[nq + 1], float32[size], int64[size]; valid while
+        this object lives."""
+        lims, D, I = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(_lib.load().knn_range_device(self._h, C.byref(lims), C.byref(D), C.byref(I)),
+                   "knn_range_device")
+        return lims.value or 0, D.value or 0, I.value or 0
+
+    def to_host(self):
+        """(lims, D, I) as numpy arrays, faiss's range_search return."""
+        lims = np.empty(self.nq + 1, dtype=np.int64)
+        D = np.empty(self.size, dtype=np.float32)
+        I = np.empty(self.size, dtype=np.int64)
+        _lib.check(_lib.load().knn_range_copy(self._h, _ptr(lims), _ptr(D), _ptr(I)),
+                   "knn_range_copy")
+        return lims, D, I
 
 
 class Index:
@@ -167,6 +206,27 @@ class Index:
             _lib.check(_lib.load().knn_search(self._h, _ptr(x), n, k, _ptr(D), _ptr(I)),
                        "knn_search")
         return D, I
+
+    def range_search(self, x, thresh: float):
+        """faiss ``index.range_search(x, thresh) -> (lims, D, I)``: every stored row with squared
+        L2 distance < thresh (L2) or inner product > thresh (IP / cosine).  Query i's hits are
+        ``D[lims[i]:lims[i+1]]`` / ``I[lims[i]:lims[i+1]]``, best first, exact ties by the smaller
+        label (faiss leaves the order unspecified), so a k-prefix of a segment is a top-k."""
+        x = _as_matrix(x, self.d, "range_search")
+        lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(lib.knn_range_search(self._h, _ptr(x), x.shape[0], float(thresh), C.byref(h)),
+                   "knn_range_search")
+        return RangeResult(h).to_host()
+
+    def range_search_device(self, q_ptr: int, nq: int, thresh: float, stream: int = 0) -> "RangeResult":
+        """range_search over nq device-resident queries on `stream`; the result stays on the
+        index's device (``RangeResult.device_ptrs()``) until the returned object is dropped."""
+        h = C.c_void_p()
+        _lib.check(_lib.load().knn_range_search_device(self._h, C.c_void_p(q_ptr), int(nq),
+                                                       float(thresh), C.c_void_p(stream or None),
+                                                       C.byref(h)), "knn_range_search_device")
+        return RangeResult(h)
 
     def reset(self) -> None:
         _lib.check(_lib.load().knn_reset(self._h), "knn_reset")
@@ -336,6 +396,6 @@ def read_index(fname, device: int = -1, devices=None) -> Index:
     return cls._wrap(h)
 
 
-__all__ = ["Index", "IndexFlat", "IndexFlatL2", "IndexFlatIP", "IndexHNSWFlat", "IndexIVFPQ",
+__all__ = ["Index", "RangeResult", "IndexFlat", "IndexFlatL2", "IndexFlatIP", "IndexHNSWFlat", "IndexIVFPQ",
            "normalize_L2", "read_index", "write_index", "METRIC_L2", "METRIC_INNER_PRODUCT",
            "METRIC_COSINE", "KnnError"]

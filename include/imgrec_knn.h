@@ -11,6 +11,8 @@
  *   knn_add / knn_add_device             index.add(arr)                main/create_index.py:311
  *   knn_search / knn_search_device       index.search(query_vec, k)    main/search_from_image.py:247,
  *                                                                      Analytics/rt_Search.py:63
+ *   knn_range_search / _device           index.range_search(x, thresh) (every faiss flat index; the
+ *                                                                      near-duplicate query)
  *   knn_ntotal / knn_dim                 index.ntotal / index.d        main/search_from_image.py:340,
  *                                                                      main/create_index.py:321
  *   knn_write                            faiss.write_index(index, f)   main/create_index.py:320
@@ -168,6 +170,46 @@ int knn_search(knn_index_t* index, const float* q_host, int64_t nq, int k,
                float* D_host, int64_t* I_host);
 int knn_search_device(knn_index_t* index, const float* q_dev, int64_t nq, int k,
                       float* D_dev, int64_t* I_dev, void* stream);
+
+/* Range search (faiss Index::range_search): every stored row within a radius of each query.
+ *   - L2: the rows whose fp32 key (|q|^2 + |x|^2) - 2 q.x, clamped at 0, is < radius (squared L2,
+ *     as knn_search returns it).  IP / COSINE: the rows with q.x > radius (cosine normalises rows
+ *     and queries on entry, as knn_search does); D holds the inner product.  Both comparisons are
+ *     strict, as in faiss.  A pair whose key is NaN is never returned.
+ *   - Layout, as faiss's RangeSearchResult: lims is int64[nq + 1] with lims[0] = 0; query i's hits
+ *     are D[lims[i] .. lims[i + 1]) (float32) and I[lims[i] .. lims[i + 1]) (int64, row offset +
+ *     id_offset).
+ *   - Order (faiss leaves it unspecified): knn_search's — best first, exact ties by the smaller
+ *     label.  The output is deterministic, and its first k entries are a valid top-k.
+ *   - Arithmetic: exact fp32, no candidate pass and no certificate.  A pair's key depends on
+ *     (q, x, d, metric) only — not on ntotal, nq, the query's place in the batch or the row
+ *     sharding — so the same pair gets the same bits from any call (it need not equal the bits
+ *     knn_search returns for the pair: that kernel's summation order depends on its launch plan).
+ *   - nq = 0 gives lims = {0}; an empty index, or L2 with radius <= 0, gives all-zero lims;
+ *     radius = +inf (L2) / -inf (IP) returns every stored row for every query.  A NaN radius is
+ *     KNN_EINVAL.  So is a shard of 2^32 rows or more, and a chunk of 8192 queries with 2^32 hits
+ *     or more ("lower the radius or split the batch"): entries pack a 32-bit row beside the key.
+ * The result object owns device buffers on the index's device (devices[0] of a multi-device
+ * index, which searches its shards concurrently and merges per query into the same order). */
+typedef struct knn_range_result knn_range_result_t;
+/* faiss Index::range_search.  Host queries; waits; result buffers live on the index's device. */
+int knn_range_search(knn_index_t* index, const float* q_host, int64_t nq, float radius,
+                     knn_range_result_t** out);
+/* Device queries on `stream`.  Unlike the other *_device calls this one waits once on the stream
+ * (per chunk of 8192 queries): the result size must reach the host before the result can be
+ * allocated.  The last kernels may still run when it returns; knn_range_copy and
+ * knn_range_device wait for them. */
+int knn_range_search_device(knn_index_t* index, const float* q_dev, int64_t nq, float radius,
+                            void* stream, knn_range_result_t** out);
+int64_t knn_range_nq(const knn_range_result_t* result);
+int64_t knn_range_size(const knn_range_result_t* result);     /* = lims[nq] */
+/* Host copies; any pointer may be NULL. */
+int knn_range_copy(const knn_range_result_t* result, int64_t* lims, float* D, int64_t* I);
+/* Device pointers, valid until knn_range_free (D and I are never NULL; an empty result's hold one
+ * unused element). */
+int knn_range_device(const knn_range_result_t* result, const int64_t** lims, const float** D,
+                     const int64_t** I);
+int knn_range_free(knn_range_result_t* result);
 
 /* Merge nlists candidate lists per query into the top k.  cand_D/cand_I are laid out
  * [nlists][nq][kin] (the layout of an all-gather of per-shard [nq][kin] results); entries with

@@ -46,6 +46,8 @@ SIGNATURES = {
     "knn_reconstruct_n": (_i, [_vp, _i64, _i64, _vp]),
     "knn_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "knn_search_device": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "knn_search_filtered": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp]),
+    "knn_search_filtered_device": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _vp, _vp]),
     "knn_range_search": (_i, [_vp, _vp, _i64, _f, C.POINTER(_vp)]),
     "knn_range_search_device": (_i, [_vp, _vp, _i64, _f, _vp, C.POINTER(_vp)]),
     "knn_range_nq": (_i64, [_vp]),

@@ -337,10 +337,28 @@ void free_single(knn_index* ix) {
     largek_free(ix);
     hugek_free(ix);
     range_free(ix);
+    filter_free(ix);
     for (hipEvent_t e : ix->ev) (void)hipEventDestroy(e);
     if (ix->fence) (void)hipEventDestroy(ix->fence);
     (void)hipStreamDestroy(ix->stream);
     delete ix;
+}
+
+// The host form's inputs onto the index's device, on its own stream: the queries into hq, room for
+// the results in hd / hi, and the bitmap's bytes that can matter (bits at or past ntotal are
+// ignored: *nbits is lowered to ntotal) into ft_bits.
+int filtered_stage_host(knn_index* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
+                        int64_t* nbits) {
+    int rc;
+    *nbits = std::min(*nbits, ix->ntotal);
+    const size_t nbytes = (size_t)((*nbits + 7) / 8);
+    if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)nq * ix->d)) != KNN_OK) return rc;
+    if ((rc = grow(&ix->hd, &ix->hd_cap, (size_t)nq * k)) != KNN_OK) return rc;
+    if ((rc = grow(&ix->hi, &ix->hi_cap, (size_t)nq * k)) != KNN_OK) return rc;
+    if ((rc = grow(&ix->ft_bits, &ix->ft_bits_cap, std::max<size_t>(nbytes, 1))) != KNN_OK) return rc;
+    KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+    if (nbytes) KNN_HIP(hipMemcpyAsync(ix->ft_bits, bitmap, nbytes, hipMemcpyHostToDevice, ix->stream));
+    return KNN_OK;
 }
 
 int set_metric(knn_index* ix, int metric) {
@@ -614,6 +632,48 @@ int knn_range_device(const knn_range_result_t* r, const int64_t** lims, const fl
 int knn_range_free(knn_range_result_t* r) {
     range_result_free(r);
     return KNN_OK;
+}
+
+static int filtered_args_ok(knn_index_t* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
+                            int64_t nbits, const float* D, const int64_t* I) {
+    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
+    if (k <= 0) KNN_FAIL(KNN_EINVAL, "k must be >= 1 (got %d)", k);
+    if (nbits < 0) KNN_FAIL(KNN_EINVAL, "nbits must be >= 0 (got %lld)", (long long)nbits);
+    if (nbits > 0 && !bitmap) KNN_FAIL(KNN_EINVAL, "bitmap is NULL with nbits = %lld", (long long)nbits);
+    if (nq < 0 || (nq > 0 && (!q || !D || !I))) KNN_FAIL(KNN_EINVAL, "bad query/output pointers");
+    return KNN_OK;
+}
+
+int knn_search_filtered_device(knn_index_t* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
+                               int64_t nbits, float* D, int64_t* I, void* stream) {
+    int rc;
+    if ((rc = filtered_args_ok(ix, q, nq, k, bitmap, nbits, D, I)) != KNN_OK) return rc;
+    if (nq == 0) return KNN_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    if (ix->multi) return multi_search_filtered(ix, q, false, nq, k, bitmap, nbits, D, I, st);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
+    if ((rc = filtered_search_locked(ix, q, nq, k, bitmap, nbits, nullptr, D, I, st)) != KNN_OK) return rc;
+    return fence_end(ix, st);
+}
+
+int knn_search_filtered(knn_index_t* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
+                        int64_t nbits, float* D, int64_t* I) {
+    int rc;
+    if ((rc = filtered_args_ok(ix, q, nq, k, bitmap, nbits, D, I)) != KNN_OK) return rc;
+    if (nq == 0) return KNN_OK;
+    if (ix->multi) return multi_search_filtered(ix, q, true, nq, k, bitmap, nbits, D, I, nullptr);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
+    if ((rc = filtered_stage_host(ix, q, nq, k, bitmap, &nbits)) != KNN_OK) return rc;
+    if ((rc = filtered_search_locked(ix, ix->hq, nq, k, ix->ft_bits, nbits, nullptr, ix->hd, ix->hi,
+                                     ix->stream)) != KNN_OK) return rc;
+    KNN_HIP(hipMemcpyAsync(D, ix->hd, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    KNN_HIP(hipMemcpyAsync(I, ix->hi, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
+    KNN_HIP(hipStreamSynchronize(ix->stream));
+    return fence_end_synced(ix);
 }
 
 int knn_merge_device(const float* cD, const int64_t* cI, int nlists, int64_t nq, int kin, int k,

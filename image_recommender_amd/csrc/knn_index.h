@@ -1,7 +1,7 @@
 // knn_index.h — internal state of one k-NN index and the helpers the C-ABI translation units
 // share (knn_capi.cpp: entry points; knn_plan.cpp: launch geometry and error-bound coefficients;
 // knn_search.cpp: the search paths; knn_io.cpp: the faiss file layout; knn_multi.cpp: one index
-// over several devices; knn_range.hip: range search).  Not part of the public ABI
+// over several devices; knn_range.hip: range search; knn_filter.hip: filtered search).  Not part of the public ABI
 // (include/imgrec_knn.h).
 #pragma once
 
@@ -237,6 +237,15 @@ struct knn_index {
     uint32_t* rg_cur = nullptr; size_t rg_cur_cap = 0;
     unsigned long long* rg_total = nullptr; size_t rg_total_cap = 0;
     unsigned long long* rg_total_h = nullptr;
+    // filtered search (knn_filter.hip): the compacted list of the selected rows (padded to a whole
+    // tile), the compaction's per-block counts / offsets, the selected count on the device and in
+    // page-locked host memory (read by the k > KNN_MAX_K route only), and the host form's device
+    // copy of the bitmap
+    uint32_t* ft_list = nullptr; size_t ft_list_cap = 0;
+    uint32_t* ft_blk = nullptr; size_t ft_blk_cap = 0;
+    uint32_t* ft_m = nullptr; size_t ft_m_cap = 0;
+    uint32_t* ft_m_h = nullptr;
+    uint8_t* ft_bits = nullptr; size_t ft_bits_cap = 0;
 };
 
 // One range search's result (knn_range_search): buffers on `device`, complete once `done` fires.
@@ -263,6 +272,8 @@ int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st);
 int ensure_split(knn_index* ix, hipStream_t st);
 int ensure_i8(knn_index* ix, hipStream_t st);
 int create_single(int d, int metric, int device, knn_index** out);
+int filtered_stage_host(knn_index* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
+                        int64_t* nbits);
 void free_single(knn_index* ix);
 // knn_search.cpp
 int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
@@ -313,5 +324,11 @@ int range_result_from_host(int device, int64_t nq, const int64_t* lims, const fl
                            hipStream_t st, knn_range_result** out);
 void range_result_free(knn_range_result* r);
 void range_free(knn_index* ix);
+// knn_filter.hip: the k best rows among those the bitmap selects (device bitmap, IDSelectorBitmap
+// layout; bit lmap[r] for local row r when lmap is given, a shard's local -> global map), for the
+// nq device queries on `st`; labels are row + id_offset.  Waits once only when k > KNN_MAX_K.
+int filtered_search_locked(knn_index* ix, const float* q, int64_t nq, int k, const uint8_t* bits,
+                           int64_t nbits, const int64_t* lmap, float* D, int64_t* I, hipStream_t st);
+void filter_free(knn_index* ix);
 
 }  // namespace imgrec

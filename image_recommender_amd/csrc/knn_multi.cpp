@@ -34,6 +34,8 @@ struct knn_multi {
     std::vector<size_t> sd_cap;
     std::vector<int64_t*> si;
     std::vector<size_t> si_cap;
+    std::vector<uint8_t*> sb;                    // per shard: bitmap copy (other devices only)
+    std::vector<size_t> sb_cap;
     std::vector<float*> sx;                      // per shard: row staging for add_device
     std::vector<size_t> sx_cap;
     std::vector<hipEvent_t> done;                // per shard (its device)
@@ -119,6 +121,8 @@ int multi_create(int d, int metric, const int* devices, int ndev, knn_index** ou
     m->sd_cap.assign(ndev, 0);
     m->si.assign(ndev, nullptr);
     m->si_cap.assign(ndev, 0);
+    m->sb.assign(ndev, nullptr);
+    m->sb_cap.assign(ndev, 0);
     m->sx.assign(ndev, nullptr);
     m->sx_cap.assign(ndev, 0);
     m->done.assign(ndev, nullptr);
@@ -160,7 +164,7 @@ int multi_free(knn_index* ix) {
         DeviceGuard g(m->devices[s]);
         (void)hipDeviceSynchronize();
         for (void* p : {(void*)m->lmap[s], (void*)m->sq[s], (void*)m->sd[s], (void*)m->si[s],
-                        (void*)m->sx[s]})
+                        (void*)m->sx[s], (void*)m->sb[s]})
             if (p) (void)hipFree(p);
         if (m->done[s]) (void)hipEventDestroy(m->done[s]);
     }
@@ -265,9 +269,11 @@ int multi_reconstruct_n(knn_index* ix, int64_t i0, int64_t n, float* x) {
 namespace {
 
 // Every shard searches q (device pointer on the first device, ready when m->ready fires) into the
-// gather buffer; the first device's stream `st` then merges into D, I.
+// gather buffer; the first device's stream `st` then merges into D, I.  With `filtered`, the
+// search among the rows the bitmap `bits` (first device, global rows) selects.
 int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
-                   hipStream_t st) {
+                   hipStream_t st, bool filtered = false, const uint8_t* bits = nullptr,
+                   int64_t nbits = 0) {
     knn_multi* m = M(ix);
     const int ndev = (int)m->shards.size();
     const size_t nk = (size_t)nq * k;
@@ -299,7 +305,19 @@ int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, i
             ds = m->sd[s];
             is = m->si[s];
         }
-        if ((rc = search_locked(sh, qs, nq, k, ds, is, ss)) != KNN_OK) return rc;
+        if (filtered) {
+            const uint8_t* bs = bits;
+            const size_t nbytes = (size_t)((nbits + 7) / 8);
+            if (!local && nbytes) {
+                if ((rc = grow(&m->sb[s], &m->sb_cap[s], nbytes)) != KNN_OK) return rc;
+                KNN_HIP(hipMemcpyPeerAsync(m->sb[s], sh->device, bits, ix->device, nbytes, ss));
+                bs = m->sb[s];
+            }
+            rc = filtered_search_locked(sh, qs, nq, k, bs, nbits, m->lmap[s], ds, is, ss);
+        } else {
+            rc = search_locked(sh, qs, nq, k, ds, is, ss);
+        }
+        if (rc != KNN_OK) return rc;
         KNN_HIP(launch_map_labels(is, (int64_t)nk, m->lmap[s], ix->id_offset, ss));
         if (!local) {
             KNN_HIP(hipMemcpyPeerAsync(m->gD + s * nk, ix->device, ds, sh->device,
@@ -359,6 +377,36 @@ int multi_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int
     KNN_HIP(hipMemcpyAsync(I, ix->hi, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost,
                            ix->stream));
     KNN_HIP(hipStreamSynchronize(ix->stream));
+    return fence_end_synced(ix);
+}
+
+int multi_search_filtered(knn_index* ix, const float* q, bool q_on_host, int64_t nq, int k,
+                          const uint8_t* bitmap, int64_t nbits, float* D, int64_t* I, hipStream_t st) {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    if (q_on_host) st = ix->stream;
+    const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
+    int rc;
+    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
+    float* Dd = D;
+    int64_t* Id = I;
+    if (q_on_host) {
+        if ((rc = filtered_stage_host(ix, q, nq, k, bitmap, &nbits)) != KNN_OK) return rc;
+        q = ix->hq;
+        bitmap = ix->ft_bits;
+        Dd = ix->hd;
+        Id = ix->hi;
+    }
+    nbits = std::min(nbits, ix->ntotal);         // bits at or past ntotal are ignored
+    if (ix->ntotal == 0 || nbits == 0) {
+        KNN_HIP(launch_fill_empty(Dd, Id, nq * (int64_t)k, kmetric, st));
+    } else if ((rc = fan_out_search(ix, q, nq, k, Dd, Id, st, true, bitmap, nbits)) != KNN_OK) {
+        return rc;
+    }
+    if (!q_on_host) return fence_end(ix, st);
+    KNN_HIP(hipMemcpyAsync(D, Dd, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+    KNN_HIP(hipMemcpyAsync(I, Id, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    KNN_HIP(hipStreamSynchronize(st));
     return fence_end_synced(ix);
 }
 

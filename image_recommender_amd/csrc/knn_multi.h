@@ -22,6 +22,11 @@ int multi_search_device(knn_index* ix, const float* q, int64_t nq, int k, float*
 // order; q on the host (q_on_host; `st` unused) or on the first device, ready on `st`
 int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq, float radius,
                        hipStream_t st, knn_range_result** out);
+// filtered search: the bitmap (global rows; on the host with q when q_on_host, else on the first
+// device, ready on `st`) reaches every shard's device, every shard compacts it through its local ->
+// global map and searches concurrently; merged as multi_search merges
+int multi_search_filtered(knn_index* ix, const float* q, bool q_on_host, int64_t nq, int k,
+                          const uint8_t* bitmap, int64_t nbits, float* D, int64_t* I, hipStream_t st);
 int multi_set_metric(knn_index* ix, int metric);
 int multi_set_trained(knn_index* ix, bool trained);
 int multi_set_timing(knn_index* ix, int enable);

@@ -23,6 +23,12 @@ Beyond the reference's own calls, ``index.range_search(x, thresh) -> (lims, D, I
 flat index has it: all rows within a radius, the near-duplicate query) is served by every class
 here, multi-device indexes included; ``sharded.ShardedIndex`` and ``ivfpq`` do not have it.
 
+``index.search(x, k, params=SearchParameters(sel=selector))`` is faiss's filtered search: the k
+nearest rows among the ids the selector keeps (``IDSelectorRange`` / ``Batch`` / ``Array`` /
+``Bitmap`` / ``All`` / ``Not`` / ``And`` / ``Or`` / ``XOr``).  A selector is lowered on the host to
+one bitmap over the stored rows and the search walks only the selected rows
+(include/imgrec_knn.h knn_search_filtered).  ``range_search`` does not take a selector.
+
 Semantics: every index class here is an EXACT flat index (the north_star parity target is
 ``IndexFlatL2``).  ``IndexHNSWFlat`` and ``IndexIVFPQ`` keep their constructor signatures and
 attributes (``hnsw.efSearch``, ``nprobe``, ``nlist``, ...) so the reference code runs unchanged,
@@ -84,6 +90,173 @@ def _device_list(device: int, devices):
     if not devices:
         raise ValueError("devices must list at least one device")
     return devices
+
+
+# ---- id selectors and search parameters (faiss 1.10 constructors) ---------------------------
+class IDSelector:
+    """A set of labels.  ``is_member(id)`` tests one; ``to_bitmap(n, offset=0)`` lowers the set to
+    faiss IDSelectorBitmap's layout over the labels [offset, offset + n): bit i (byte i >> 3, bit
+    i & 7) is ``is_member(offset + i)``, uint8[ceil(n / 8)].  Ids outside that range are silently
+    not members."""
+
+    def is_member(self, id: int) -> bool:      # noqa: A002 - faiss's argument name
+        raise NotImplementedError
+
+    def _mask(self, n: int, offset: int) -> np.ndarray:
+        """bool[n]: membership of the labels offset .. offset + n - 1."""
+        raise NotImplementedError
+
+    def to_bitmap(self, n: int, offset: int = 0) -> np.ndarray:
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        return np.packbits(self._mask(n, int(offset)), bitorder="little")
+
+
+def _id_array(ids, n=None) -> np.ndarray:
+    """faiss's (ids) and swig's (n, ids) constructor forms."""
+    if n is not None:
+        ids, n = n, ids
+    a = np.ascontiguousarray(np.asarray(ids).reshape(-1), dtype=np.int64)
+    return a if n is None else a[:int(n)]
+
+
+class IDSelectorRange(IDSelector):
+    """Labels in [imin, imax)."""
+
+    def __init__(self, imin: int, imax: int, assume_sorted: bool = False):
+        self.imin, self.imax, self.assume_sorted = int(imin), int(imax), bool(assume_sorted)
+
+    def is_member(self, id: int) -> bool:      # noqa: A002
+        return self.imin <= int(id) < self.imax
+
+    def _mask(self, n, offset):
+        m = np.zeros(n, dtype=bool)
+        lo, hi = max(self.imin - offset, 0), min(self.imax - offset, n)
+        if lo < hi:
+            m[lo:hi] = True
+        return m
+
+
+class IDSelectorArray(IDSelector):
+    """The listed labels (``IDSelectorArray(ids)`` or ``(n, ids)``)."""
+
+    def __init__(self, ids, n=None):
+        self.ids = _id_array(ids, n)
+        self._set = None
+
+    def is_member(self, id: int) -> bool:      # noqa: A002
+        if self._set is None:
+            self._set = set(self.ids.tolist())
+        return int(id) in self._set
+
+    def _mask(self, n, offset):
+        m = np.zeros(n, dtype=bool)
+        local = self.ids - offset
+        m[local[(local >= 0) & (local < n)]] = True
+        return m
+
+
+class IDSelectorBatch(IDSelectorArray):
+    """The listed labels (faiss keeps them in a hash set with a Bloom filter; the set is the same)."""
+
+
+class IDSelectorBitmap(IDSelector):
+    """Label i is a member iff byte i >> 3 exists and its bit i & 7 is set
+    (``IDSelectorBitmap(bitmap)`` or ``(nbytes, bitmap)``)."""
+
+    def __init__(self, bitmap, n=None):
+        if n is not None:
+            bitmap, n = n, bitmap
+        b = np.ascontiguousarray(np.asarray(bitmap).reshape(-1), dtype=np.uint8)
+        self.bitmap = b if n is None else b[:int(n)]
+        self.n = int(self.bitmap.size)
+
+    def is_member(self, id: int) -> bool:      # noqa: A002
+        i = int(id)
+        return 0 <= (i >> 3) < self.n and bool((int(self.bitmap[i >> 3]) >> (i & 7)) & 1)
+
+    def _mask(self, n, offset):
+        m = np.zeros(n, dtype=bool)
+        bits = np.unpackbits(self.bitmap, bitorder="little").astype(bool)
+        lo, hi = max(offset, 0), min(offset + n, bits.size)
+        if lo < hi:
+            m[lo - offset:hi - offset] = bits[lo:hi]
+        return m
+
+
+class IDSelectorAll(IDSelector):
+    def is_member(self, id: int) -> bool:      # noqa: A002
+        return True
+
+    def _mask(self, n, offset):
+        return np.ones(n, dtype=bool)
+
+
+class IDSelectorNot(IDSelector):
+    def __init__(self, sel: IDSelector):
+        self.sel = sel
+
+    def is_member(self, id: int) -> bool:      # noqa: A002
+        return not self.sel.is_member(id)
+
+    def _mask(self, n, offset):
+        return ~self.sel._mask(n, offset)
+
+
+class _IDSelectorPair(IDSelector):
+    _op = None
+
+    def __init__(self, lhs: IDSelector, rhs: IDSelector):
+        self.lhs, self.rhs = lhs, rhs
+
+    def is_member(self, id: int) -> bool:      # noqa: A002
+        return bool(type(self)._op(self.lhs.is_member(id), self.rhs.is_member(id)))
+
+    def _mask(self, n, offset):
+        return type(self)._op(self.lhs._mask(n, offset), self.rhs._mask(n, offset))
+
+
+class IDSelectorAnd(_IDSelectorPair):
+    _op = staticmethod(lambda a, b: a & b)
+
+
+class IDSelectorOr(_IDSelectorPair):
+    _op = staticmethod(lambda a, b: a | b)
+
+
+class IDSelectorXOr(_IDSelectorPair):
+    _op = staticmethod(lambda a, b: a ^ b)
+
+
+class SearchParameters:
+    """faiss.SearchParameters: ``sel`` restricts a search to the selector's labels."""
+
+    def __init__(self, sel: IDSelector | None = None):
+        self.sel = sel
+
+
+class SearchParametersIVF(SearchParameters):
+    """Constructor-compatible; the extra fields are recorded and ignored (these classes search
+    exactly)."""
+
+    def __init__(self, sel=None, nprobe: int = 1, max_codes: int = 0, quantizer_params=None,
+                 inverted_list_context=None):
+        super().__init__(sel)
+        self.nprobe, self.max_codes = int(nprobe), int(max_codes)
+        self.quantizer_params, self.inverted_list_context = quantizer_params, inverted_list_context
+
+
+class SearchParametersHNSW(SearchParameters):
+    """Constructor-compatible; the extra fields are recorded and ignored (these classes search
+    exactly)."""
+
+    def __init__(self, sel=None, efSearch: int = 16, check_relative_distance: bool = True,
+                 bounded_queue: bool = True):
+        super().__init__(sel)
+        self.efSearch = int(efSearch)
+        self.check_relative_distance = bool(check_relative_distance)
+        self.bounded_queue = bool(bounded_queue)
 
 
 class RangeResult:
@@ -191,7 +364,10 @@ class Index:
             raise RuntimeError("Error in add: index is not trained (call train first)")
         _lib.check(_lib.load().knn_add(self._h, _ptr(x), x.shape[0]), "knn_add")
 
-    def search(self, x, k: int, *, D=None, I=None):
+    def search(self, x, k: int, *, params=None, D=None, I=None):
+        """faiss ``index.search(x, k[, params=SearchParameters(sel=...)])``.  With a selector the
+        result is the k nearest among the selected labels (label -1 past their number), from the
+        filtered kernels (include/imgrec_knn.h knn_search_filtered); without one nothing changes."""
         x = _as_matrix(x, self.d, "search")
         k = int(k)
         if k <= 0:
@@ -202,16 +378,27 @@ class Index:
         if D.shape != (n, k) or I.shape != (n, k) or D.dtype != np.float32 or I.dtype != np.int64 \
                 or not D.flags.c_contiguous or not I.flags.c_contiguous:
             raise ValueError("D/I must be C-contiguous float32/int64 arrays of shape (n, k)")
-        if n:
+        sel = getattr(params, "sel", None)
+        if n and sel is not None:
+            nbits = self.ntotal
+            bitmap = np.ascontiguousarray(sel.to_bitmap(nbits, getattr(self, "_id_offset", 0)),
+                                          dtype=np.uint8)
+            _lib.check(_lib.load().knn_search_filtered(self._h, _ptr(x), n, k, _ptr(bitmap), nbits,
+                                                       _ptr(D), _ptr(I)), "knn_search_filtered")
+        elif n:
             _lib.check(_lib.load().knn_search(self._h, _ptr(x), n, k, _ptr(D), _ptr(I)),
                        "knn_search")
         return D, I
 
-    def range_search(self, x, thresh: float):
+    def range_search(self, x, thresh: float, *, params=None):
         """faiss ``index.range_search(x, thresh) -> (lims, D, I)``: every stored row with squared
         L2 distance < thresh (L2) or inner product > thresh (IP / cosine).  Query i's hits are
         ``D[lims[i]:lims[i+1]]`` / ``I[lims[i]:lims[i+1]]``, best first, exact ties by the smaller
-        label (faiss leaves the order unspecified), so a k-prefix of a segment is a top-k."""
+        label (faiss leaves the order unspecified), so a k-prefix of a segment is a top-k.
+        A selector in ``params`` is not supported here."""
+        if getattr(params, "sel", None) is not None:
+            raise NotImplementedError("range_search does not take an id selector; the filtered form "
+                                      "that exists is search(x, k, params=SearchParameters(sel=...))")
         x = _as_matrix(x, self.d, "range_search")
         lib = _lib.load()
         h = C.c_void_p()
@@ -252,8 +439,18 @@ class Index:
                                                  C.c_void_p(d_ptr), C.c_void_p(i_ptr),
                                                  C.c_void_p(stream or None)), "knn_search_device")
 
+    def search_filtered_device(self, q_ptr: int, nq: int, k: int, bitmap_ptr: int, nbits: int,
+                               d_ptr: int, i_ptr: int, stream: int = 0) -> None:
+        """The filtered search over device-resident queries, bitmap (over the stored rows: bit i is
+        row i, label i + id offset) and outputs on `stream`; never waits while k <= KNN_MAX_K."""
+        _lib.check(_lib.load().knn_search_filtered_device(
+            self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(bitmap_ptr or None), int(nbits),
+            C.c_void_p(d_ptr), C.c_void_p(i_ptr), C.c_void_p(stream or None)),
+            "knn_search_filtered_device")
+
     def set_id_offset(self, off: int) -> None:
         _lib.check(_lib.load().knn_set_id_offset(self._h, int(off)), "knn_set_id_offset")
+        self._id_offset = int(off)      # selectors speak labels: lowered with this offset
 
     def reserve(self, n: int) -> None:
         _lib.check(_lib.load().knn_reserve(self._h, int(n)), "knn_reserve")
@@ -396,6 +593,9 @@ def read_index(fname, device: int = -1, devices=None) -> Index:
     return cls._wrap(h)
 
 
-__all__ = ["Index", "RangeResult", "IndexFlat", "IndexFlatL2", "IndexFlatIP", "IndexHNSWFlat", "IndexIVFPQ",
+__all__ = ["IDSelector", "IDSelectorRange", "IDSelectorBatch", "IDSelectorArray", "IDSelectorBitmap",
+           "IDSelectorAll", "IDSelectorNot", "IDSelectorAnd", "IDSelectorOr", "IDSelectorXOr",
+           "SearchParameters", "SearchParametersIVF", "SearchParametersHNSW",
+           "Index", "RangeResult", "IndexFlat", "IndexFlatL2", "IndexFlatIP", "IndexHNSWFlat", "IndexIVFPQ",
            "normalize_L2", "read_index", "write_index", "METRIC_L2", "METRIC_INNER_PRODUCT",
            "METRIC_COSINE", "KnnError"]

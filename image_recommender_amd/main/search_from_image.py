@@ -14,7 +14,10 @@ Deliberate changes:
 * when ``index_hnsw_<canonical>.faiss`` is absent, an index built from the same types in another
   order is used, with the query concatenated in that build order (read from the builder's
   ``.meta.json``), fixing the build/search order mismatch of Appendix C.1;
-* ``search_similar_images`` also returns the result list it plots.
+* ``search_similar_images`` also returns the result list it plots;
+* ``exclude_query`` / ``restrict_to`` (CLI ``--exclude-query`` / ``--within PREFIX``) search among
+  the stored images other than the query images / under a path prefix: one id selector lowered
+  from the resident offset->image_id map (faiss_compat filtered search), no larger-k retry loop.
 Colour features missing from the DB are computed by the HIP histogram kernel
 (vector_scripts.create_color_vector); SIFT-VLAD and DreamSim features come from the DB cache (their
 extractors need trained artefacts / pretrained weights that are not part of this path).
@@ -52,6 +55,8 @@ class ImageRecommender:
         top_k=5,
         device=-1,
         index_dir=None,
+        exclude_query=False,
+        restrict_to=None,
     ):
         self.base_dir = Path().expanduser().resolve()
         self.images_root = (self.base_dir / images_root).resolve()
@@ -64,7 +69,11 @@ class ImageRecommender:
         self.sift_n_clusters = sift_n_clusters
         self.sift_desc_dim = sift_desc_dim
         self.top_k = top_k
+        self.exclude_query = bool(exclude_query)
+        # a path prefix relative to images_root, as the images table stores paths
+        self.restrict_to = None if restrict_to is None else str(restrict_to)
         self._indexes: dict = {}       # canonical -> (index, offset_table, build_order, id_map)
+        self._within: dict = {}        # canonical -> bool[ntotal]: offsets under restrict_to
         logging.basicConfig(level=logging.INFO, format="%(asctime)s [%(levelname)s] %(message)s")
 
     # ---- DB cache (search_from_image.py:50-125) ------------------------------------------------
@@ -160,13 +169,40 @@ class ImageRecommender:
         query_vec = self._extract_query_vector(paths_rel, build_order)
         if query_vec is None:
             return None
-        distances, indices = index.search(query_vec, self.top_k)
+        sel = self._selector(canonical, id_map, paths_rel)
+        if sel is None:
+            distances, indices = index.search(query_vec, self.top_k)
+        else:
+            distances, indices = index.search(query_vec, self.top_k,
+                                              params=faiss.SearchParameters(sel=sel))
         results = self._fetch_results(indices, distances, offset_table, id_map)
         if not results:
             logging.error("No similar images found.")
             return None
         self._plot_results(query_image_paths, results)
         return results
+
+    def _selector(self, canonical, id_map, paths_rel):
+        """exclude_query / restrict_to as one id selector over the index's offsets (None = plain
+        search).  The prefix's offsets are computed once per index and kept; the query images' ids
+        are looked up by path, never by a scan of the offsets table."""
+        if not self.exclude_query and self.restrict_to is None:
+            return None
+        keep = np.ones(len(id_map), dtype=bool)
+        conn = sqlite3.connect(self.db_path)
+        if self.restrict_to is not None:
+            if canonical not in self._within:
+                ids = [r[0] for r in conn.execute(
+                    "SELECT id FROM images WHERE substr(path, 1, ?) = ?",
+                    (len(self.restrict_to), self.restrict_to))]
+                self._within[canonical] = np.isin(id_map, np.asarray(ids, dtype=np.int64))
+            keep &= self._within[canonical]
+        if self.exclude_query:
+            qids = [r[0] for p in paths_rel
+                    for r in conn.execute("SELECT id FROM images WHERE path = ?", (p,))]
+            keep &= ~np.isin(id_map, np.asarray(qids, dtype=np.int64))
+        conn.close()
+        return faiss.IDSelectorBitmap(np.packbits(keep, bitorder="little"))
 
     def _get_ordered_index_types(self, index_type: str):
         requested = [x.strip() for x in index_type.lower().split(",")]
@@ -326,9 +362,14 @@ def main(argv=None):
     ap.add_argument("--index", default="color", help="comma-separated types, e.g. color,dreamsim")
     ap.add_argument("--top-k", type=int, default=5)
     ap.add_argument("--no-plot", action="store_true")
+    ap.add_argument("--exclude-query", action="store_true",
+                    help="never return the query images themselves")
+    ap.add_argument("--within", metavar="PREFIX", default=None,
+                    help="only images whose stored path starts with PREFIX")
     a = ap.parse_args(argv)
     idx = a.index[len("combo_"):] if a.index.startswith("combo_") else a.index
-    rec = ImageRecommender(images_root=a.images_root, db_path=a.db_path, top_k=a.top_k)
+    rec = ImageRecommender(images_root=a.images_root, db_path=a.db_path, top_k=a.top_k,
+                           exclude_query=a.exclude_query, restrict_to=a.within)
     if a.no_plot:
         rec._plot_results = lambda *args, **kw: None
     res = rec.search_similar_images(a.query, index_type=idx.replace("_", ","))

@@ -211,6 +211,38 @@ int knn_range_device(const knn_range_result_t* result, const int64_t** lims, con
                      const int64_t** I);
 int knn_range_free(knn_range_result_t* result);
 
+/* Filtered search (faiss SearchParameters::sel): the k nearest rows among the rows a bitmap selects.
+ *   - Bitmap: faiss IDSelectorBitmap's layout.  Stored row i (label i + id_offset) is selected iff
+ *     i < nbits and (bitmap[i >> 3] >> (i & 7)) & 1.  The bitmap holds ceil(nbits / 8) bytes; rows
+ *     at or past nbits are unselected, bits at or past ntotal are ignored.  One bitmap serves every
+ *     query of the call.  For a multi-device index it addresses global rows and, in the device
+ *     form, lives on devices[0].
+ *   - Result: knn_search's in every respect except the candidate set: nq * k, best first, exact
+ *     ties by the smaller label.  When fewer than k rows are selected the tail holds label -1 and
+ *     +-FLT_MAX (zero selected, an empty index and nbits = 0 included).  A pair whose key is NaN
+ *     is never returned.
+ *   - Arithmetic: exact fp32, no candidate pass and no certificate.  A pair's key is the bits
+ *     knn_range_search returns for it (the same MFMA, the same depth order, chosen from the row
+ *     stride alone, the same fmaf(-2, q.x, |q|^2 + |x|^2) clamped at 0), so a result does not
+ *     depend on ntotal, the batch, the mask's other bits, the order of adds or the sharding.
+ *   - Cost: the rows are compacted into a list once per call (work proportional to ntotal bits)
+ *     and the distance kernel walks that list: its work follows the number of selected rows.
+ *   - Errors: KNN_EINVAL for k <= 0, nbits < 0, a NULL bitmap with nbits > 0, NULL queries or
+ *     outputs with nq > 0, and a shard of 2^32 rows or more.
+ *   - Waiting: the host form synchronises before it returns.  The device form enqueues on
+ *     `stream` and never waits for the GPU while k <= KNN_MAX_K (the selected count stays on the
+ *     device); stream ordering and fences are those of knn_search_device.  For k > KNN_MAX_K
+ *     (every selected pair's key, one segmented sort: coverage of faiss's k range, not a fast path)
+ *     the selected count must reach the host to size the sort: that route waits once per call on
+ *     the stream (a multi-device index: once per shard).
+ *   - Reports: knn_set_timing / knn_kernel_time cover the gathered tile kernel; knn_last_path
+ *     reports 0 after a filtered search. */
+int knn_search_filtered(knn_index_t* index, const float* q_host, int64_t nq, int k,
+                        const uint8_t* bitmap_host, int64_t nbits, float* D_host, int64_t* I_host);
+int knn_search_filtered_device(knn_index_t* index, const float* q_dev, int64_t nq, int k,
+                               const uint8_t* bitmap_dev, int64_t nbits, float* D_dev,
+                               int64_t* I_dev, void* stream);
+
 /* Merge nlists candidate lists per query into the top k.  cand_D/cand_I are laid out
  * [nlists][nq][kin] (the layout of an all-gather of per-shard [nq][kin] results); entries with
  * label -1 are ignored.  Output nq*k, same ordering/padding rules as knn_search. */

@@ -381,21 +381,41 @@ int vit_gemm_splits(int M, int N, int cus) {
 
 }  // namespace imgrec
 
+namespace {
+int device_cus() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess)
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus > 0 ? cus : 256;
+}
+}  // namespace
+
+extern "C" int vit_linear_splits(int64_t m, int n) {
+    using namespace imgrec;
+    if (m <= 0 || n <= 0 || n % kBN != 0 || m > INT32_MAX / 2) return -1;
+    return vit_gemm_splits((int)m, n, device_cus());
+}
+
 extern "C" int vit_linear_bf16(const uint16_t* x, const uint16_t* w, const float* bias, int64_t m,
                                int k, int n, int act, uint16_t* y, void* stream) {
+    return vit_linear_bf16_split(x, w, bias, m, k, n, act, 0, y, stream);
+}
+
+extern "C" int vit_linear_bf16_split(const uint16_t* x, const uint16_t* w, const float* bias,
+                                     int64_t m, int k, int n, int act, int nsplit_arg, uint16_t* y,
+                                     void* stream) {
     using namespace imgrec;
     if (!x || !w || !y || m < 0 || k <= 0 || n <= 0) return -1;
     if (k % 64 != 0 || n % kBN != 0 || m > INT32_MAX / 2) return -1;
     if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)bias) & 15) return -1;
     // 32-bit DMA offsets: a tile's rows and a weight block stay below 4 GiB
     if ((int64_t)kBM * k * 2 >= ((int64_t)1 << 31)) return -1;
+    // a caller's split count: every split owns at least one token tile (the kernel's block map
+    // and the grid size both follow from it)
+    if (nsplit_arg < 0 || (nsplit_arg > 0 && nsplit_arg > (m + kBM - 1) / kBM)) return -1;
     if (m == 0) return 0;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (cus <= 0) cus = 256;
     const int nqb = n / kBN;
-    const int nsplit = vit_gemm_splits((int)m, n, cus);
+    const int nsplit = nsplit_arg > 0 ? nsplit_arg : vit_gemm_splits((int)m, n, device_cus());
     const dim3 grid((unsigned)(nqb * nsplit)), block(kNW * 64);
     const uint32_t* xw = reinterpret_cast<const uint32_t*>(x);
     const uint32_t* ww = reinterpret_cast<const uint32_t*>(w);

@@ -65,6 +65,17 @@ enum vit_act {
 int vit_linear_bf16(const uint16_t* x, const uint16_t* w, const float* bias, int64_t m, int k,
                     int n, int act, uint16_t* y, void* stream);
 
+/* vit_linear_bf16 with the token split count chosen by the caller: each of the nsplit groups of
+ * workgroups walks the 256-row token tiles s, s + nsplit, ... (the result does not depend on it:
+ * every output element comes from one workgroup in a fixed k order).  nsplit = 0 takes the
+ * automatic choice; otherwise 1 <= nsplit <= ceil(m / 256), anything else returns -1. */
+int vit_linear_bf16_split(const uint16_t* x, const uint16_t* w, const float* bias, int64_t m,
+                          int k, int n, int act, int nsplit, uint16_t* y, void* stream);
+
+/* The token split count vit_linear_bf16 chooses for (m, n) on the current device (-1 on bad
+ * arguments: m <= 0, n not a positive multiple of 256). */
+int vit_linear_splits(int64_t m, int n);
+
 #ifdef __cplusplus
 }
 #endif

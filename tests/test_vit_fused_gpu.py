@@ -109,21 +109,19 @@ def test_patchify_and_tokens_match_torch(gpu):
 @pytest.mark.parametrize("b,n,heads", [(3, 197, 12), (2, 16, 2), (1, 1, 1), (2, 50, 3), (1, 256, 4),
                                        (4, 33, 12), (2, 208, 1), (1, 17, 5)])
 def test_attention_matches_torch(gpu, b, n, heads):
-    """vit_attention_bf16 against torch's fp32 SDPA on the same bf16 q / k / v: within the bf16
-    rounding of the probabilities (the P.V products take bf16 P) and of the output."""
+    """vit_attention_bf16 (through the forward's _attn) against the float64 softmax(q k^T / 8) v
+    of the same bf16 q / k / v, within the bound derived in tests/vit_check.py."""
     from image_recommender_amd.vector_scripts.create_dreamsim_vector import _attn
+    from tests import vit_check as vc
     g = torch.Generator(device="cuda").manual_seed(b * 1000 + n * 10 + heads)
     qkv = (torch.randn(b, n, 3 * heads * 64, device="cuda", generator=g) * 1.5).bfloat16()
-    q, k, v = qkv.float().view(b, n, 3, heads, 64).permute(2, 0, 3, 1, 4).unbind(0)
-    ref = torch.nn.functional.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(b, n, heads * 64)
     out = _attn(qkv, heads)
     torch.cuda.synchronize()
-    err = (out.float() - ref).abs()
-    # |P_bf16 - P| <= 2^-9 P per entry, so |sum (P_bf16 - P) v| <= 2^-9 max|v|; plus the output's
-    # own bf16 rounding
-    vmax = v.abs().amax(dim=(-2, -1))                    # (b, heads)
-    bound = 2.0 ** -8 * ref.abs() + 2.0 ** -8 * vmax.repeat_interleave(64, dim=1)[:, None, :] + 1e-5
-    assert float((err - bound).max()) <= 0.0, float(err.max())
+    # bf16's unit roundoff is 2^-8: |P_bf16 - P| <= 2^-8 P per entry, so |sum (P_bf16 - P) v| <=
+    # 2^-8 P|v| (the attention-weighted mean of |v|, not max|v|); plus the output's own bf16
+    # rounding 2^-8 |ref| and the fp32 slack 2^-22 (1 + smax) P|v|
+    ratio = vc.worst_ratio(out, qkv, heads, 0.125)
+    assert ratio <= 1.0, ratio
 
 
 def test_attention_rejects_bad_shapes(gpu):

@@ -43,6 +43,7 @@ SIGNATURES = {
     "knn_add_device": (_i, [_vp, _vp, _i64, _vp]),
     "knn_reserve": (_i, [_vp, _i64]),
     "knn_reset": (_i, [_vp]),
+    "knn_remove_ids": (_i, [_vp, _vp, _i64, _pi64]),
     "knn_reconstruct_n": (_i, [_vp, _i64, _i64, _vp]),
     "knn_search": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "knn_search_device": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),

@@ -304,6 +304,12 @@ int create_single(int d, int metric, int device, knn_index** out) {
         const long long v = std::atoll(e);
         if (v > 0) ix->range_cap0 = (size_t)v;
     }
+    // IMGREC_REMOVE_CHUNK=<rows> (tests): rows per bounce chunk of remove_ids, so small shapes run
+    // several chunks
+    if (const char* e = test_knob("IMGREC_REMOVE_CHUNK")) {
+        const long long v = std::atoll(e);
+        if (v > 0) ix->remove_chunk = (int64_t)v;
+    }
     if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ix->fence, hipEventDisableTiming) != hipSuccess) {
         if (ix->stream) (void)hipStreamDestroy(ix->stream);
@@ -338,6 +344,7 @@ void free_single(knn_index* ix) {
     hugek_free(ix);
     range_free(ix);
     filter_free(ix);
+    remove_free(ix);
     for (hipEvent_t e : ix->ev) (void)hipEventDestroy(e);
     if (ix->fence) (void)hipEventDestroy(ix->fence);
     (void)hipStreamDestroy(ix->stream);
@@ -474,6 +481,34 @@ int knn_reset(knn_index_t* ix) {
     ix->ntotal = 0;
     ix->xn_max_stale = true;
     return KNN_OK;
+}
+
+int knn_remove_ids(knn_index_t* ix, const uint8_t* bitmap, int64_t nbits, int64_t* nremoved) {
+    if (nremoved) *nremoved = 0;
+    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
+    if (nbits < 0) KNN_FAIL(KNN_EINVAL, "nbits must be >= 0 (got %lld)", (long long)nbits);
+    if (nbits > 0 && !bitmap) KNN_FAIL(KNN_EINVAL, "bitmap is NULL with nbits = %lld", (long long)nbits);
+    int64_t n = 0;
+    if (ix->multi) {
+        const int rc = multi_remove_ids(ix, bitmap, nbits, &n);
+        if (rc == KNN_OK && nremoved) *nremoved = n;
+        return rc;
+    }
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    int rc;
+    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
+    nbits = std::min(nbits, ix->ntotal);             // bits at or past ntotal are ignored
+    if (nbits > 0) {
+        const size_t nbytes = (size_t)((nbits + 7) / 8);
+        if ((rc = grow(&ix->ft_bits, &ix->ft_bits_cap, nbytes)) != KNN_OK) return rc;
+        KNN_HIP(hipMemcpyAsync(ix->ft_bits, bitmap, nbytes, hipMemcpyHostToDevice, ix->stream));
+        if ((rc = remove_rows_locked(ix, ix->ft_bits, nbits, nullptr, nullptr, ix->stream, &n)) != KNN_OK)
+            return rc;
+    }
+    KNN_HIP(hipStreamSynchronize(ix->stream));
+    if (nremoved) *nremoved = n;
+    return fence_end_synced(ix);
 }
 
 int knn_reconstruct_n(const knn_index_t* cix, int64_t i0, int64_t n, float* x) {

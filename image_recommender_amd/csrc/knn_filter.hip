@@ -6,7 +6,8 @@
 //      filter_scan_kernel (one workgroup: exclusive scan of the block counts, the count m, and the
 //      list's tail padded to 256 entries with row 0) and filter_scatter_kernel -> the ascending
 //      list of the selected local rows (uint32) and m, both in device memory.  On a shard of a
-//      multi-device index the bit of local row r is bit lmap[r] of the global bitmap.
+//      multi-device index the bit of local row r is bit lmap[r] of the global bitmap.  (remove_ids,
+//      knn_remove.hip, runs the same compaction on the inverted bitmap: compact_rows.)
 //   2. knn_filter_tile_kernel per query chunk: the contraction of knn_range_tile_kernel
 //      (v_mfma_f32_32x32x2_f32, the same stage depth, geometries, depth order and block map), but
 //      tile t holds the list entries [t BM, (t + 1) BM): every lane's 16-B DMA source is
@@ -69,12 +70,23 @@ __device__ __forceinline__ uint32_t filter_word(const uint8_t* __restrict__ bm, 
     return bits;
 }
 
+// invert (remove_ids' survivors): the stored rows of the word whose bit is clear
+__device__ __forceinline__ uint32_t comp_word(const uint8_t* __restrict__ bm, int64_t nbits,
+                                              const int64_t* __restrict__ lmap, int64_t ntotal,
+                                              int64_t w, int invert) {
+    const uint32_t bits = filter_word(bm, nbits, lmap, ntotal, w);
+    if (!invert) return bits;
+    const int64_t left = ntotal - w * 32;
+    const uint32_t stored = left >= 32 ? ~0u : (left > 0 ? (1u << (int)left) - 1u : 0u);
+    return ~bits & stored;
+}
+
 __global__ void __launch_bounds__(kCompThreads)
 filter_count_kernel(const uint8_t* __restrict__ bm, int64_t nbits, const int64_t* __restrict__ lmap,
-                    int64_t ntotal, uint32_t* __restrict__ blk) {
+                    int64_t ntotal, int invert, uint32_t* __restrict__ blk) {
     __shared__ int part[kCompThreads / 64];
     const int t = threadIdx.x;
-    const uint32_t w = filter_word(bm, nbits, lmap, ntotal, (int64_t)blockIdx.x * kCompThreads + t);
+    const uint32_t w = comp_word(bm, nbits, lmap, ntotal, (int64_t)blockIdx.x * kCompThreads + t, invert);
     const int s = wave_sum_i32(__popc(w));
     if ((t & 63) == 0) part[t >> 6] = s;
     __syncthreads();
@@ -111,11 +123,12 @@ filter_scan_kernel(uint32_t* __restrict__ blk, int nblk, uint32_t* __restrict__ 
 
 __global__ void __launch_bounds__(kCompThreads)
 filter_scatter_kernel(const uint8_t* __restrict__ bm, int64_t nbits, const int64_t* __restrict__ lmap,
-                      int64_t ntotal, const uint32_t* __restrict__ blk, uint32_t* __restrict__ list) {
+                      int64_t ntotal, int invert, const uint32_t* __restrict__ blk,
+                      uint32_t* __restrict__ list) {
     __shared__ int part[kCompThreads / 64];
     const int t = threadIdx.x;
     const int64_t wi = (int64_t)blockIdx.x * kCompThreads + t;
-    uint32_t w = filter_word(bm, nbits, lmap, ntotal, wi);
+    uint32_t w = comp_word(bm, nbits, lmap, ntotal, wi, invert);
     const int c = __popc(w);
     const int ex = wave_excl_scan_i32(c);
     const int s = wave_sum_i32(c);
@@ -510,19 +523,20 @@ hipError_t launch_filter_tile(const FilterPlan& p, const FilterArgs& a, hipStrea
 constexpr int64_t kFilterSortEntries = int64_t(1) << 27;
 constexpr int64_t kFilterSortMaxQ = 65535;         // the unpack grid's y extent
 
-int compact(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lmap, hipStream_t st) {
+int compact(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lmap, bool invert,
+            hipStream_t st) {
     int rc;
     const int nblk = (int)((ix->ntotal + kCompRows - 1) / kCompRows);
     if ((rc = grow(&ix->ft_list, &ix->ft_list_cap, (size_t)round_up(ix->ntotal, 256) + 256)) != KNN_OK) return rc;
     if ((rc = grow(&ix->ft_blk, &ix->ft_blk_cap, (size_t)nblk)) != KNN_OK) return rc;
     if ((rc = grow(&ix->ft_m, &ix->ft_m_cap, (size_t)1)) != KNN_OK) return rc;
     hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)nblk), dim3(kCompThreads), 0, st, bits, nbits,
-                       lmap, ix->ntotal, ix->ft_blk);
+                       lmap, ix->ntotal, invert ? 1 : 0, ix->ft_blk);
     KNN_HIP(hipGetLastError());
     hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(256), 0, st, ix->ft_blk, nblk, ix->ft_m, ix->ft_list);
     KNN_HIP(hipGetLastError());
     hipLaunchKernelGGL(filter_scatter_kernel, dim3((unsigned)nblk), dim3(kCompThreads), 0, st, bits, nbits,
-                       lmap, ix->ntotal, ix->ft_blk, ix->ft_list);
+                       lmap, ix->ntotal, invert ? 1 : 0, ix->ft_blk, ix->ft_list);
     KNN_HIP(hipGetLastError());
     return KNN_OK;
 }
@@ -623,8 +637,13 @@ int filtered_search_locked(knn_index* ix, const float* q, int64_t nq, int k, con
         return KNN_OK;
     }
     int rc;
-    if ((rc = compact(ix, bits, nbits, lmap, st)) != KNN_OK) return rc;
+    if ((rc = compact(ix, bits, nbits, lmap, false, st)) != KNN_OK) return rc;
     return k <= KNN_MAX_K ? filtered_lists(ix, q, nq, k, D, I, st) : filtered_sorted(ix, q, nq, k, D, I, st);
+}
+
+int compact_rows(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lmap, bool invert,
+                 hipStream_t st) {
+    return compact(ix, bits, nbits, lmap, invert, st);
 }
 
 void filter_free(knn_index* ix) {

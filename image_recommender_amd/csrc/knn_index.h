@@ -1,7 +1,8 @@
 // knn_index.h — internal state of one k-NN index and the helpers the C-ABI translation units
 // share (knn_capi.cpp: entry points; knn_plan.cpp: launch geometry and error-bound coefficients;
 // knn_search.cpp: the search paths; knn_io.cpp: the faiss file layout; knn_multi.cpp: one index
-// over several devices; knn_range.hip: range search; knn_filter.hip: filtered search).  Not part of the public ABI
+// over several devices; knn_range.hip: range search; knn_filter.hip: filtered search;
+// knn_remove.hip: remove_ids).  Not part of the public ABI
 // (include/imgrec_knn.h).
 #pragma once
 
@@ -246,6 +247,12 @@ struct knn_index {
     uint32_t* ft_m = nullptr; size_t ft_m_cap = 0;
     uint32_t* ft_m_h = nullptr;
     uint8_t* ft_bits = nullptr; size_t ft_bits_cap = 0;
+    // remove_ids (knn_remove.hip): rows per bounce chunk when > 0 (IMGREC_REMOVE_CHUNK, tests), the
+    // survivor count and first moved row in page-locked host memory, and a shard's copy of the
+    // bitmap's per-word popcount prefix (multi-device renumbering)
+    int64_t remove_chunk = 0;
+    uint32_t* rm_h = nullptr;
+    uint32_t* rm_pref = nullptr; size_t rm_pref_cap = 0;
 };
 
 // One range search's result (knn_range_search): buffers on `device`, complete once `done` fires.
@@ -330,5 +337,19 @@ void range_free(knn_index* ix);
 int filtered_search_locked(knn_index* ix, const float* q, int64_t nq, int k, const uint8_t* bits,
                            int64_t nbits, const int64_t* lmap, float* D, int64_t* I, hipStream_t st);
 void filter_free(knn_index* ix);
+// its compaction alone: ft_list = the ascending local rows whose bit is set (invert: the stored rows
+// whose bit is clear), padded with row 0 to 256 entries, and ft_m[0] = their count
+int compact_rows(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lmap, bool invert,
+                 hipStream_t st);
+// knn_remove.hip: the rows the device bitmap selects (bit lmap[r] for local row r when lmap is
+// given) leave the index in place; `extra` (or NULL) is one more array of 8-byte rows compacted with
+// them.  Waits once on `st` for the count; the moves may still run when it returns.
+int remove_rows_locked(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lmap,
+                       int64_t* extra, hipStream_t st, int64_t* nremoved);
+// lab[i] -= the set bits below lab[i] (words: the bitmap as 32-bit words, 0 at and past nbits; pref:
+// their exclusive popcount prefix; removed: every set bit)
+hipError_t launch_renumber_labels(int64_t* lab, int64_t n, const uint32_t* words, const uint32_t* pref,
+                                  int64_t nbits, int64_t removed, hipStream_t st);
+void remove_free(knn_index* ix);
 
 }  // namespace imgrec

@@ -253,6 +253,64 @@ int multi_reset(knn_index* ix) {
     return KNN_OK;
 }
 
+// Removal.  The host has the bitmap, so everything a shard cannot derive from its own rows is
+// computed here: the bitmap as 32-bit words (bits at and past nbits cleared) and the words'
+// exclusive popcount prefix.  Every shard gets both, compacts its rows and its label map with the
+// bit of each row's label (remove_rows_locked through lmap), and renumbers the surviving labels:
+// new = old - (set bits below old).  A run's survivors stay contiguous in labels and in local rows
+// (labels become dense again), so every old run maps to at most one new run.
+int multi_remove_ids(knn_index* ix, const uint8_t* bitmap, int64_t nbits, int64_t* nremoved) {
+    knn_multi* m = M(ix);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    *nremoved = 0;
+    nbits = std::min(nbits, ix->ntotal);
+    if (nbits <= 0) return KNN_OK;
+    const size_t nw = (size_t)((nbits + 31) / 32), nbytes = (size_t)((nbits + 7) / 8);
+    std::vector<uint32_t> words(nw, 0u), pref(nw + 1, 0u);
+    std::memcpy(words.data(), bitmap, nbytes);
+    if (nbits & 31) words[nw - 1] &= (1u << (int)(nbits & 31)) - 1u;
+    for (size_t w = 0; w < nw; ++w) pref[w + 1] = pref[w] + (uint32_t)__builtin_popcount(words[w]);
+    const int64_t removed = (int64_t)pref[nw];
+    if (removed == 0) return KNN_OK;
+    // set bits below label g
+    auto below = [&](int64_t g) -> int64_t {
+        if (g >= nbits) return removed;
+        return (int64_t)pref[(size_t)(g >> 5)] +
+               __builtin_popcount(words[(size_t)(g >> 5)] & ((1u << (int)(g & 31)) - 1u));
+    };
+    int rc;
+    for (size_t s = 0; s < m->shards.size(); ++s) {
+        knn_index* sh = m->shards[s];
+        if (sh->ntotal == 0) continue;
+        DeviceGuard g(sh->device);
+        std::lock_guard<std::mutex> lks(sh->mu);
+        const hipStream_t ss = sh->stream;
+        if ((rc = fence_begin(sh, ss)) != KNN_OK) return rc;
+        if ((rc = grow(&sh->ft_bits, &sh->ft_bits_cap, nw * 4)) != KNN_OK) return rc;
+        if ((rc = grow(&sh->rm_pref, &sh->rm_pref_cap, nw)) != KNN_OK) return rc;
+        KNN_HIP(hipMemcpyAsync(sh->ft_bits, words.data(), nw * 4, hipMemcpyHostToDevice, ss));
+        KNN_HIP(hipMemcpyAsync(sh->rm_pref, pref.data(), nw * 4, hipMemcpyHostToDevice, ss));
+        int64_t gone = 0;
+        if ((rc = remove_rows_locked(sh, sh->ft_bits, nbits, m->lmap[s], m->lmap[s], ss, &gone)) != KNN_OK)
+            return rc;
+        KNN_HIP(launch_renumber_labels(m->lmap[s], sh->ntotal, reinterpret_cast<const uint32_t*>(sh->ft_bits),
+                                       sh->rm_pref, nbits, removed, ss));
+        KNN_HIP(hipStreamSynchronize(ss));
+        if ((rc = fence_end_synced(sh)) != KNN_OK) return rc;
+    }
+    std::vector<knn_multi::Run> runs;
+    std::vector<int64_t> local(m->shards.size(), 0);
+    for (const auto& r : m->runs) {
+        const int64_t b0 = below(r.g0), keep = r.n - (below(r.g0 + r.n) - b0);
+        if (keep > 0) runs.push_back({r.g0 - b0, r.shard, local[r.shard], keep});
+        local[r.shard] += keep;
+    }
+    m->runs.swap(runs);
+    ix->ntotal -= removed;
+    *nremoved = removed;
+    return KNN_OK;
+}
+
 int multi_reconstruct_n(knn_index* ix, int64_t i0, int64_t n, float* x) {
     knn_multi* m = M(ix);
     std::lock_guard<std::mutex> lk(ix->mu);

@@ -27,6 +27,10 @@ int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq
 // global map and searches concurrently; merged as multi_search merges
 int multi_search_filtered(knn_index* ix, const float* q, bool q_on_host, int64_t nq, int k,
                           const uint8_t* bitmap, int64_t nbits, float* D, int64_t* I, hipStream_t st);
+// remove_ids: the host bitmap addresses global rows; every shard compacts its own rows and its label
+// map through that map, the surviving labels are renumbered densely and the runs rebuilt.  Shards
+// may end up holding different numbers of rows.  Waits.
+int multi_remove_ids(knn_index* ix, const uint8_t* bitmap, int64_t nbits, int64_t* nremoved);
 int multi_set_metric(knn_index* ix, int metric);
 int multi_set_trained(knn_index* ix, bool trained);
 int multi_set_timing(knn_index* ix, int enable);

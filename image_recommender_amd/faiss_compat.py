@@ -29,6 +29,18 @@ nearest rows among the ids the selector keeps (``IDSelectorRange`` / ``Batch`` /
 one bitmap over the stored rows and the search walks only the selected rows
 (include/imgrec_knn.h knn_search_filtered).  ``range_search`` does not take a selector.
 
+``index.remove_ids(sel_or_ids) -> nremoved`` (faiss ``IndexFlatCodes::remove_ids``) deletes rows in
+place: survivors keep their order and are renumbered densely, and the stored rows and every derived
+copy are compacted on the device without re-adding anything (include/imgrec_knn.h knn_remove_ids).
+
+================================  =================================================================
+beyond the reference's calls      served by
+================================  =================================================================
+``index.range_search(x, thresh)`` knn_range_search (csrc/knn_range.hip)
+``index.search(x, k, params=..)`` knn_search_filtered (csrc/knn_filter.hip)
+``index.remove_ids(sel_or_ids)``  knn_remove_ids (csrc/knn_remove.hip)
+================================  =================================================================
+
 Semantics: every index class here is an EXACT flat index (the north_star parity target is
 ``IndexFlatL2``).  ``IndexHNSWFlat`` and ``IndexIVFPQ`` keep their constructor signatures and
 attributes (``hnsw.efSearch``, ``nprobe``, ``nlist``, ...) so the reference code runs unchanged,
@@ -259,6 +271,15 @@ class SearchParametersHNSW(SearchParameters):
         self.bounded_queue = bool(bounded_queue)
 
 
+def _removal_bitmap(sel_or_ids, ntotal: int, id_offset: int = 0) -> np.ndarray:
+    """The bitmap ``remove_ids`` hands to the library: uint8[ceil(ntotal / 8)], bit i set iff the
+    stored row i (label ``i + id_offset``) is to be removed.  `sel_or_ids` is an ``IDSelector`` or an
+    array of labels (faiss's wrapper turns an array into an ``IDSelectorBatch``); duplicates and
+    labels outside the index are ignored."""
+    sel = sel_or_ids if isinstance(sel_or_ids, IDSelector) else IDSelectorBatch(sel_or_ids)
+    return np.ascontiguousarray(sel.to_bitmap(int(ntotal), int(id_offset)), dtype=np.uint8)
+
+
 class RangeResult:
     """A range search's device-resident result (include/imgrec_knn.h knn_range_result_t): owns the
     handle and frees it when dropped."""
@@ -417,6 +438,19 @@ class Index:
 
     def reset(self) -> None:
         _lib.check(_lib.load().knn_reset(self._h), "knn_reset")
+
+    def remove_ids(self, sel) -> int:
+        """faiss ``index.remove_ids(sel) -> nremoved``: the rows whose labels an ``IDSelector`` (or
+        an array of labels) names leave the index.  Survivors keep their order and their labels
+        become dense again (row offset + id offset), as in faiss's flat indexes.  The removal runs
+        in place on the device (include/imgrec_knn.h knn_remove_ids), multi-device indexes included.
+        Out of scope: ``sharded.ShardedIndex`` and ``ivfpq`` have no ``remove_ids``."""
+        nbits = self.ntotal
+        bitmap = _removal_bitmap(sel, nbits, getattr(self, "_id_offset", 0))
+        removed = C.c_int64()
+        _lib.check(_lib.load().knn_remove_ids(self._h, _ptr(bitmap), nbits, C.byref(removed)),
+                   "knn_remove_ids")
+        return int(removed.value)
 
     def reconstruct_n(self, i0: int = 0, n: int | None = None) -> np.ndarray:
         n = self.ntotal - i0 if n is None else n

@@ -20,6 +20,11 @@ the offsets (:269-320, Appendix C.2); rows missing any part are skipped (inner J
 BLOB fails to decode is skipped with a warning (:181-185).
 CLI: ``python -m image_recommender_amd.main.create_index --db-path images.db --vector-types color
 sift dreamsim`` — the flags the reference README documents (README.md:101-110) but never parses.
+
+Beyond the reference: ``--sync`` (``FAISSIndexBuilderDB.sync_index``) brings an existing index file
+up to date with the database in place — rows of images that left the database are removed with
+``index.remove_ids``, only the new images are fetched, decoded and added — instead of the full
+re-ingest (``plan_sync`` is the plan, a pure function).
 """
 from __future__ import annotations
 
@@ -39,6 +44,22 @@ from .. import faiss_compat as faiss
 from ..ingest import decode_rows, scan_native
 
 os.environ.setdefault("KMP_DUPLICATE_LIB_OK", "TRUE")
+
+
+def plan_sync(indexed, current_ids):
+    """What a sync has to do: ``(remove_offsets, kept_pairs, new_ids)``.
+
+    `indexed` is the offsets table, ``[(image_id, offset), ...]``; `current_ids` the ids that have a
+    complete record now.  ``remove_offsets``: the offsets (ascending) of indexed images that are no
+    longer current.  ``kept_pairs``: the surviving ``(image_id, new offset)`` in their old order,
+    new offsets dense from 0 (what ``remove_ids`` leaves).  ``new_ids``: the current ids that are
+    not indexed, ascending; they are appended after the survivors."""
+    current = set(int(i) for i in current_ids)
+    by_offset = sorted(((int(i), int(o)) for i, o in indexed), key=lambda p: p[1])
+    remove_offsets = [o for i, o in by_offset if i not in current]
+    kept_pairs = [(i, n) for n, i in enumerate(i for i, _ in by_offset if i in current)]
+    new_ids = sorted(current - {i for i, _ in by_offset})
+    return remove_offsets, kept_pairs, new_ids
 
 
 class FAISSIndexBuilderDB:
@@ -286,6 +307,81 @@ class FAISSIndexBuilderDB:
         return index
 
 
+    # ---- sync: the index file brought up to date in place -----------------------------------------
+    def sync_index(self):
+        """Bring the existing index file and offsets table up to date with the database without
+        re-ingesting it: the rows of images that no longer have a complete record are removed in
+        place (``index.remove_ids``), the images that are not indexed yet are fetched, decoded and
+        appended in ascending id order, the offsets table is replaced in one transaction and the
+        index and meta files are rewritten.  Returns the index, or None (with an error logged and
+        the advice to rebuild) when the file and the table do not describe each other: the table's
+        offsets are not exactly 0..ntotal-1 of the file, the meta file's vector types differ, or
+        the dimension differs.  Nothing is written in that case.
+
+        Matching is by image id only: a vector that changed under an unchanged id is not detected
+        (rebuild for that).  When every new id is greater than every indexed id (AUTOINCREMENT's
+        normal case) the index file and the offsets table are the full rebuild's, byte for byte."""
+        combo = "_".join(self.vector_types)
+        self._log(f"Starting FAISS index sync for [{combo}]…", level="info")
+
+        def refuse(why):
+            self._log(f"Cannot sync {self.index_file}: {why}; run a full rebuild (build_index).",
+                      level="error")
+            return None
+
+        meta_path = Path(str(self.index_file) + ".meta.json")
+        if not self.index_file.exists() or not meta_path.exists():
+            return refuse("the index file or its meta file is missing")
+        meta = json.loads(meta_path.read_text())
+        if list(meta.get("vector_types", [])) != self.vector_types:
+            return refuse(f"it was built for {meta.get('vector_types')}, not {self.vector_types}")
+        index = faiss.read_index(str(self.index_file), device=self.device)
+        part_dims = meta.get("part_dims")
+        now_dims = self._probe_part_dims()
+        if int(meta.get("dim", -1)) != int(index.d) or \
+                (now_dims is not None and int(sum(now_dims)) != int(index.d)):
+            return refuse(f"the dimension differs (file {index.d}, meta {meta.get('dim')}, "
+                          f"database {None if now_dims is None else int(sum(now_dims))})")
+        indexed = self.read_cur.execute(f"SELECT image_id, offset FROM {self.offset_table}").fetchall()
+        if sorted(o for _, o in indexed) != list(range(index.ntotal)):
+            return refuse(f"the offsets of {self.offset_table} are not exactly 0..{index.ntotal - 1}")
+        _, join_strs = self._make_select_and_joins()
+        current = [r[0] for r in self.read_cur.execute(f"SELECT i.id FROM images i {join_strs}")]
+        remove_offsets, pairs, new_ids = plan_sync(indexed, current)
+        self._log(f"{len(remove_offsets)} vectors to remove, {len(pairs)} kept, {len(new_ids)} "
+                  f"images to add.", level="info")
+
+        if remove_offsets:
+            removed = index.remove_ids(np.asarray(remove_offsets, dtype=np.int64))
+            if removed != len(remove_offsets) or index.ntotal != len(pairs):
+                return refuse(f"remove_ids removed {removed} of {len(remove_offsets)} rows")
+        for b0 in range(0, len(new_ids), self.batch_size):
+            rows = sorted(self._refetch(new_ids[b0:b0 + self.batch_size]), key=lambda r: r[0])
+            ids, arr, part_dims = self._process_batch(rows, part_dims)
+            if len(ids) == 0:
+                continue
+            if arr.shape[1] != index.d:
+                return refuse(f"the dimension differs (file {index.d}, new rows {arr.shape[1]})")
+            start = index.ntotal
+            index.add(arr)
+            pairs += [(int(rid), start + i) for i, rid in enumerate(ids)]
+            self._log(f"Added {len(ids)} vectors (total {index.ntotal}).", level="info")
+
+        # one transaction: a reader sees the old table or the new one
+        with self.write_conn:
+            self.write_conn.execute(f"DELETE FROM {self.offset_table}")
+            self.write_conn.executemany(
+                f"INSERT INTO {self.offset_table} (image_id, offset) VALUES (?, ?)", pairs)
+        self._log(f"Writing FAISS index to {self.index_file.resolve()}", level="info")
+        faiss.write_index(index, str(self.index_file))
+        self._write_meta(int(index.d), part_dims)
+        self._log(f"Index synced ({index.ntotal} vectors).", level="info")
+        self.read_conn.close()
+        self.write_conn.close()
+        self._log("Done.", level="info")
+        return index
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Build the exact MI355X k-NN index from images.db")
     ap.add_argument("--db-path", default="images.db")
@@ -296,12 +392,19 @@ def main(argv=None):
     ap.add_argument("--efConstruction", type=int, default=200)
     ap.add_argument("--efSearch", type=int, default=64)
     ap.add_argument("--update-index", action="store_true")
+    ap.add_argument("--sync", action="store_true",
+                    help="bring the existing index up to date in place (remove deleted images, add "
+                         "new ones) instead of rebuilding it")
     ap.add_argument("--device", type=int, default=-1)
     a = ap.parse_args(argv)
     types = [t for v in a.vector_types for t in v.split(",") if t]
-    FAISSIndexBuilderDB(db_path=a.db_path, vector_types=types, batch_size=a.batch_size,
-                        index_file=a.output, hnsw_M=a.hnsw_M, efConstruction=a.efConstruction,
-                        efSearch=a.efSearch, device=a.device).build_index(update_index=a.update_index)
+    builder = FAISSIndexBuilderDB(db_path=a.db_path, vector_types=types, batch_size=a.batch_size,
+                                  index_file=a.output, hnsw_M=a.hnsw_M, efConstruction=a.efConstruction,
+                                  efSearch=a.efSearch, device=a.device)
+    if a.sync:
+        builder.sync_index()
+    else:
+        builder.build_index(update_index=a.update_index)
 
 
 if __name__ == "__main__":

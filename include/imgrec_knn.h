@@ -162,6 +162,21 @@ int knn_add_device(knn_index_t* index, const float* x_dev, int64_t n, void* stre
 int knn_reserve(knn_index_t* index, int64_t n);
 int knn_reset(knn_index_t* index);
 
+/* faiss Index::remove_ids on a bitmap over the stored rows (knn_search_filtered's layout and rules:
+ * row i is removed iff i < nbits and bit i is set; bits at or past ntotal are ignored).  Survivors keep
+ * their order; labels become dense again (row offset + id_offset).  Host bitmap; waits.
+ *   - In place (csrc/knn_remove.hip): the fp32 rows, the norms and every derived copy that exists
+ *     (bf16, split, int8) are compacted by moving row bytes through a bounded bounce buffer (the
+ *     64 MB add staging), so no copy is re-derived and memory does not grow with ntotal; the state
+ *     afterwards is the one the same adds without the removed rows would have left.
+ *   - *nremoved (may be NULL) receives the number of rows removed.  An empty index, nbits = 0 or no
+ *     set bit remove nothing and return KNN_OK; removing every row leaves a usable empty index.
+ *   - KNN_EINVAL for a NULL index, nbits < 0, and a NULL bitmap with nbits > 0.
+ *   - Exclusive, like knn_add: ordered after earlier operations on any stream.
+ *   - A multi-device index: the bitmap addresses global rows; every shard compacts its own rows, so
+ *     shards may afterwards hold different numbers of rows (later adds are still cut evenly). */
+int knn_remove_ids(knn_index_t* index, const uint8_t* bitmap_host, int64_t nbits, int64_t* nremoved);
+
 /* Copy rows [i0, i0+n) back to the host as stored (normalised for COSINE). */
 int knn_reconstruct_n(const knn_index_t* index, int64_t i0, int64_t n, float* x_host);
 

@@ -22,6 +22,14 @@ KNN_SEARCH_AUTO, KNN_SEARCH_EXACT, KNN_SEARCH_SPLIT, KNN_SEARCH_BF16, KNN_SEARCH
 KNN_FENCE_EAGER, KNN_FENCE_LAZY = 0, 1
 COLOR_HIST_MAX_BINS = 32
 INGEST_NOT_FAST, INGEST_TOO_SMALL = -1, -2
+KMEANS_SPHERICAL = 1          # include/imgrec_kmeans.h
+KMEANS_STATS_PER_ITER = 8
+
+
+class KmeansParams(C.Structure):
+    """kmeans_params_t of include/imgrec_kmeans.h."""
+    _fields_ = [("niter", C.c_int), ("nredo", C.c_int), ("spherical", C.c_int), ("verbose", C.c_int),
+                ("seed", C.c_int64), ("device", C.c_int)]
 
 # (name, restype, argtypes) of every exported symbol — also the list the CPU test checks against
 # the headers.
@@ -80,6 +88,11 @@ SIGNATURES = {
     "knn_large_k_fallbacks": (_i, [_vp, C.POINTER(_i64)]),
     "knn_last_error": (C.c_char_p, []),
     "knn_version": (C.c_char_p, []),
+    # imgrec_kmeans.h
+    "kmeans_step_device": (_i, [_vp, _i64, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "kmeans_split_device": (_i, [_vp, _i, _i, _vp, _pi, _vp]),
+    "kmeans_train": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _pd, _vp]),
+    "kmeans_train_device": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _pd, _vp, _vp]),
     # imgrec_color.h
     "color_hist_device": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "color_hist_host": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _vp]),

@@ -17,6 +17,8 @@ reference call                    where
 ``faiss.read_index``              main/search_from_image.py:339
 ``faiss.normalize_L2``            main/search_from_image.py:322
 ``index.search(q, k)``            main/search_from_image.py:247, Analytics/rt_Search.py:63
+``faiss.Kmeans(d, k, niter=..,    vector_scripts/create_sift_vector.py:221 (``.train(x)`` at :226,
+gpu=True)``                       ``.centroids`` at :227): kmeans_train (csrc/knn_kmeans.hip)
 ================================  =================================================================
 
 Beyond the reference's own calls, ``index.range_search(x, thresh) -> (lims, D, I)`` (every faiss
@@ -591,6 +593,141 @@ class IndexIVFPQ(Index):
         self._trained = True
 
 
+class Kmeans:
+    """``faiss.Kmeans(d, k, **clustering_parameters)``: Lloyd k-means on the HIP step kernels
+    (include/imgrec_kmeans.h, csrc/knn_kmeans.hip).
+
+    The algorithm is faiss's ``Clustering::train``: per run an initialisation, then ``niter``
+    times an assignment (exact fp32, ties to the smaller centroid id), the means, faiss's
+    empty-cluster split (a donor drawn in proportion to its size, rows scaled by 1 +- 1/1024) and,
+    with ``spherical``, a row normalisation; the recorded objective of an iteration is the one of
+    its assignment, before the update; of ``nredo`` runs the best final objective is kept.
+
+    The random stream is not faiss's: the initial centroids are a seeded sample of k distinct
+    training rows (``std::mt19937_64(seed + run)``), and the subsample of more than
+    ``k * max_points_per_centroid`` rows is a seeded numpy permutation.  faiss itself is not a
+    dependency of this project, so bit parity with faiss's own runs is not pinned by any test.
+    With ``init_centroids`` given and no empty cluster the result depends on no random number, and
+    two runs on the same input give the same bytes (the update uses no float atomics).
+
+    ``gpu`` is accepted and ignored (the reference passes ``gpu=True``): everything runs on the
+    GPU.  ``int_centroids``, ``frozen_centroids`` and ``train(weights=...)`` are not implemented.
+
+    After ``train``: ``centroids`` (k, d) float32, ``obj`` (niter,) the objective per iteration,
+    ``iteration_stats`` (dicts of ``obj``, ``time``, ``time_search``, ``imbalance_factor``,
+    ``nsplit``, plus the step's GPU milliseconds ``ms_assign`` / ``ms_sort`` / ``ms_update``) and
+    ``index``, an ``IndexFlatL2`` (``IndexFlatIP`` when spherical) holding the centroids.
+    """
+
+    def __init__(self, d: int, k: int, niter: int = 25, nredo: int = 1, verbose: bool = False,
+                 spherical: bool = False, min_points_per_centroid: int = 39,
+                 max_points_per_centroid: int = 256, seed: int = 1234, gpu=False,
+                 update_index: bool = False, device: int = -1, int_centroids: bool = False,
+                 frozen_centroids: bool = False, decode_block_size: int = 32768):
+        if int_centroids:
+            raise NotImplementedError("Kmeans: int_centroids=True (centroids rounded to integers) "
+                                      "is not implemented.")
+        if frozen_centroids:
+            raise NotImplementedError("Kmeans: frozen_centroids=True (initial centroids kept fixed) "
+                                      "is not implemented.")
+        self.d, self.k = int(d), int(k)
+        if self.d <= 0 or self.k <= 0:
+            raise ValueError(f"Kmeans: d and k must be positive (got d={d}, k={k})")
+        self.niter, self.nredo = int(niter), int(nredo)
+        if self.niter <= 0 or self.nredo <= 0:
+            raise ValueError(f"Kmeans: niter and nredo must be positive (got {niter}, {nredo})")
+        self.verbose, self.spherical = bool(verbose), bool(spherical)
+        self.min_points_per_centroid = int(min_points_per_centroid)
+        self.max_points_per_centroid = int(max_points_per_centroid)
+        self.seed, self.gpu, self.update_index = int(seed), gpu, bool(update_index)
+        self.device = int(device)
+        self.decode_block_size = int(decode_block_size)
+        self.centroids = None
+        self.obj = None
+        self.iteration_stats = None
+        self.index = None
+
+    def _params(self) -> "_lib.KmeansParams":
+        return _lib.KmeansParams(self.niter, self.nredo, int(self.spherical), int(self.verbose),
+                                 self.seed, self.device)
+
+    def _init(self, init_centroids):
+        if init_centroids is None:
+            return None
+        c = np.ascontiguousarray(init_centroids, dtype=np.float32)
+        if c.shape != (self.k, self.d):
+            raise ValueError(f"init_centroids must have shape ({self.k}, {self.d}), got {c.shape}")
+        return c
+
+    def _finish(self, centroids, obj, stats) -> float:
+        self.centroids = centroids
+        st = stats.reshape(self.niter, _lib.KMEANS_STATS_PER_ITER)
+        self.obj = st[:, 0].copy()
+        self.iteration_stats = [
+            {"obj": float(r[0]), "time": float(r[1]), "time_search": float(r[2]),
+             "imbalance_factor": float(r[3]), "nsplit": int(r[4]), "ms_assign": float(r[5]),
+             "ms_sort": float(r[6]), "ms_update": float(r[7])} for r in st]
+        cls = IndexFlatIP if self.spherical else IndexFlatL2
+        self.index = cls(self.d, device=self.device)
+        self.index.add(centroids)
+        return float(obj)
+
+    def train(self, x, weights=None, init_centroids=None) -> float:
+        """Cluster the rows of x; returns the last iteration's objective."""
+        if weights is not None:
+            raise NotImplementedError("Kmeans.train: per-row weights are not implemented.")
+        x = _as_matrix(x, self.d, "Kmeans.train")
+        n, k = x.shape[0], self.k
+        if n < k:
+            raise RuntimeError(f"Number of training points ({n}) should be at least as large as "
+                               f"number of clusters ({k})")
+        c0 = self._init(init_centroids)
+        if n > k * self.max_points_per_centroid:
+            keep = k * self.max_points_per_centroid
+            if self.verbose:
+                print(f"Sampling a subset of {keep} / {n} for training")
+            perm = np.random.RandomState(self.seed).permutation(n)[:keep]
+            x = np.ascontiguousarray(x[perm])
+            n = keep
+        elif n < k * self.min_points_per_centroid:
+            import warnings
+            warnings.warn(f"clustering {n} points to {k} centroids: please provide at least "
+                          f"{k * self.min_points_per_centroid} training points", stacklevel=2)
+        centroids = np.empty((k, self.d), dtype=np.float32)
+        stats = np.zeros(self.niter * _lib.KMEANS_STATS_PER_ITER, dtype=np.float64)
+        obj = C.c_double()
+        prm = self._params()
+        _lib.check(_lib.load().kmeans_train(_ptr(x), n, self.d, k, C.byref(prm),
+                                            None if c0 is None else _ptr(c0), _ptr(centroids),
+                                            C.byref(obj), _ptr(stats)), "kmeans_train")
+        return self._finish(centroids, obj.value, stats)
+
+    def train_device(self, x_ptr: int, n: int, stream: int = 0, init_centroids=None) -> float:
+        """``train`` over n device-resident rows (row-major float32, on the current device) on
+        `stream`: no subsampling and no copy of the rows; waits for the result."""
+        n = int(n)
+        if n < self.k:
+            raise RuntimeError(f"Number of training points ({n}) should be at least as large as "
+                               f"number of clusters ({self.k})")
+        c0 = self._init(init_centroids)
+        centroids = np.empty((self.k, self.d), dtype=np.float32)
+        stats = np.zeros(self.niter * _lib.KMEANS_STATS_PER_ITER, dtype=np.float64)
+        obj = C.c_double()
+        prm = self._params()
+        _lib.check(_lib.load().kmeans_train_device(C.c_void_p(x_ptr), n, self.d, self.k, C.byref(prm),
+                                                   None if c0 is None else _ptr(c0), _ptr(centroids),
+                                                   C.byref(obj), _ptr(stats),
+                                                   C.c_void_p(stream or None)), "kmeans_train_device")
+        return self._finish(centroids, obj.value, stats)
+
+    def assign(self, x):
+        """(D.ravel(), I.ravel()) of ``index.search(x, 1)``, as in faiss."""
+        if self.centroids is None:
+            raise RuntimeError("should train before assigning")
+        D, I = self.index.search(x, 1)
+        return D.ravel(), I.ravel()
+
+
 def normalize_L2(x: np.ndarray) -> None:
     """In-place row L2 normalisation (faiss.normalize_L2; rows with norm 0 are left unchanged)."""
     if not isinstance(x, np.ndarray) or x.dtype != np.float32 or not x.flags.c_contiguous:
@@ -631,5 +768,5 @@ __all__ = ["IDSelector", "IDSelectorRange", "IDSelectorBatch", "IDSelectorArray"
            "IDSelectorAll", "IDSelectorNot", "IDSelectorAnd", "IDSelectorOr", "IDSelectorXOr",
            "SearchParameters", "SearchParametersIVF", "SearchParametersHNSW",
            "Index", "RangeResult", "IndexFlat", "IndexFlatL2", "IndexFlatIP", "IndexHNSWFlat", "IndexIVFPQ",
-           "normalize_L2", "read_index", "write_index", "METRIC_L2", "METRIC_INNER_PRODUCT",
+           "Kmeans", "normalize_L2", "read_index", "write_index", "METRIC_L2", "METRIC_INNER_PRODUCT",
            "METRIC_COSINE", "KnnError"]

@@ -63,6 +63,7 @@
 
 #include "knn_kernels.h"
 #include "lds_dma.h"
+#include "wave_ops.h"
 
 namespace imgrec {
 namespace {
@@ -244,12 +245,11 @@ knn_b16w_tile_kernel(const uint32_t* __restrict__ xh, const float* __restrict__ 
 
     // XCD-aware bijective block -> (query block, row split) map: the G query blocks of one row
     // split run on one XCD and share its L2 for the corpus tiles
-    const int nwg = gridDim.x, wg = blockIdx.x;
 #ifdef IMGREC_B16_STAMPS
+    const int wg = blockIdx.x;
     if (threadIdx.x == 0 && wg < 1024) g_b16w_wg[2 * wg] = __builtin_amdgcn_s_memrealtime();
 #endif
-    const int xcd = wg & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int wgid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (wg >> 3);
+    const int wgid = xcd_wgid();
     constexpr int kG = 4;
     const int G = (nqb % kG == 0) ? kG : nqb;
     const int qbg = wgid / (nsplit * G), rem = wgid - qbg * (nsplit * G);

@@ -8,9 +8,9 @@
 //      list of the selected local rows (uint32) and m, both in device memory.  On a shard of a
 //      multi-device index the bit of local row r is bit lmap[r] of the global bitmap.  (remove_ids,
 //      knn_remove.hip, runs the same compaction on the inverted bitmap: compact_rows.)
-//   2. knn_filter_tile_kernel per query chunk: the contraction of knn_range_tile_kernel
-//      (v_mfma_f32_32x32x2_f32, the same stage depth, geometries, depth order and block map), but
-//      tile t holds the list entries [t BM, (t + 1) BM): every lane's 16-B DMA source is
+//   2. knn_filter_tile_kernel per query chunk: the tile core of knn_tile.h, as the range kernel
+//      uses it (v_mfma_f32_32x32x2_f32, the same stage depth, geometries, depth order and block
+//      map), but tile t holds the list entries [t BM, (t + 1) BM): every lane's 16-B DMA source is
 //      xb + list[position] * dp + chunk, re-derived once per tile from the tile's list entries,
 //      which reach LDS by a DMA of their own one tile ahead.  The grid is planned on the host from
 //      ntotal; every workgroup reads m and derives its own tiles.
@@ -33,13 +33,11 @@
 #include <algorithm>
 
 #include "knn_index.h"
-#include "lds_dma.h"
+#include "knn_tile.h"
 #include "wave_ops.h"
 
 namespace imgrec {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- compaction ---------------------------------------------------------------------------------
 constexpr int kCompThreads = 256;
@@ -146,56 +144,14 @@ filter_scatter_kernel(const uint8_t* __restrict__ bm, int64_t nbits, const int64
 }
 
 // ---- the gathered tile kernel ---------------------------------------------------------------------
-// knn_range.hip's tile geometry (WR x WQ waves of 128 rows x 32 queries, BK-deep stages in an NS
-// ring, the tiles' norms in an NS ring) plus two slots of a tile's list entries.
-template <int WR, int WQ, int NS, int BK>
-struct FilterGeom {
-    static constexpr int WB = 4;
-    static constexpr int NW = WR * WQ, NT = NW * 64;
-    static constexpr int RW = 32 * WB;
-    static constexpr int BM = WR * RW, BQ = WQ * 32;
-    static constexpr int CPR = BK / 4;                 // 16-B chunks per staged row
-    static constexpr int RPP = 64 / CPR;               // rows per 1-KiB DMA piece
-    static constexpr int RPB = 64 / BK;                // rows per 256-B bank row
-    static constexpr int SA = BM * BK, SB = BQ * BK, STAGE = SA + SB;   // floats
-    static constexpr int PA = BM / RPP, PB = BQ / RPP, PIECES = PA + PB;
-    static constexpr int LPW = PIECES / NW;
-    static constexpr int LDS_FLOATS = NS * STAGE + NS * BM + 2 * BM;
-    static_assert(BK == 16 || BK == 32, "stage depth");
-    static_assert(PIECES % NW == 0, "pieces must divide evenly over waves");
-    static_assert(BM % 64 == 0, "norm and list DMAs use whole waves");
-    static_assert(NS == 2 || NS == 3, "the prologue and the vmcnt waits assume a 2- or 3-slot ring");
-    static_assert(LDS_FLOATS * 4 <= (NW == 4 || BK == 32 ? 80 : 160) * 1024, "LDS budget (two workgroups per CU)");
+// The tile core's ring (NS stages, the tiles' norms in an NS ring) plus two slots of a tile's list
+// entries; the plan's geometries at two workgroups per CU.
+template <class G>
+struct FilterLds {
+    static constexpr int FLOATS = G::LDS_FLOATS + 2 * G::BM;
+    static_assert(G::NS == 2 || G::NS == 3, "the prologue and the vmcnt waits assume a 2- or 3-slot ring");
+    static_assert(FLOATS * 4 <= (G::NW == 4 || G::BK == 32 ? 80 : 160) * 1024, "LDS budget (two workgroups per CU)");
 };
-
-__device__ __forceinline__ void dma16(const float* g, uint32_t lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
-// knn_kernels.hip's list_insert_mono: insertion into an ascending list when a lane's ids arrive
-// in increasing order, so an equal key lands behind the entries already there.
-template <int K>
-__device__ __forceinline__ void list_insert_mono(float (&kd)[K], int (&ki)[K], float d, int id) {
-    bool c[K];
-#pragma unroll
-    for (int p = 0; p < K; ++p) c[p] = d < kd[p];
-#pragma unroll
-    for (int p = K - 1; p > 0; --p) {
-        kd[p] = __builtin_amdgcn_fmed3f(kd[p - 1], d, kd[p]);
-        ki[p] = c[p - 1] ? ki[p - 1] : (c[p] ? id : ki[p]);
-    }
-    kd[0] = c[0] ? d : kd[0];
-    ki[0] = c[0] ? id : ki[0];
-}
 
 struct FilterArgs {
     const float* xb;            // corpus, row stride dp
@@ -217,19 +173,14 @@ struct FilterArgs {
 
 // KM = 16 / 32: the register-list epilogue; KM = 0: the store-everything epilogue (any k)
 template <int WR, int WQ, int NS, int BK, int KM>
-__global__ void __launch_bounds__(WR * WQ * 64, WR * WQ == 4 ? 2 : 1)
+__global__ void __launch_bounds__(WR * WQ * 64, (TileGeom<WR, WQ, NS, BK>::MIN_WAVES))
 knn_filter_tile_kernel(const FilterArgs a) {
-    using G = FilterGeom<WR, WQ, NS, BK>;
-    constexpr int WB = G::WB, RW = G::RW;
-    constexpr int NW = G::NW, BM = G::BM, BQ = G::BQ, SA = G::SA, STAGE = G::STAGE;
-    constexpr int PA = G::PA, LPW = G::LPW, CPR = G::CPR, RPP = G::RPP, RPB = G::RPB;
-    constexpr int KH = BK / 2;
+    using G = TileGeom<WR, WQ, NS, BK>;
+    constexpr int WB = G::WB, RW = G::RW, NW = G::NW, BM = G::BM, BQ = G::BQ, STAGE = G::STAGE;
+    constexpr int LPW = G::LPW;
     constexpr int KL = KM > 0 ? KM : 1;
-    __shared__ __attribute__((aligned(16))) float smem[G::LDS_FLOATS];
-    // XCD-aware block -> (query block, row split) map of the exact kernel
-    const int nwg = gridDim.x, wg = blockIdx.x;
-    const int xcd = wg & 7, qq = nwg >> 3, rr8 = nwg & 7;
-    const int wgid = (xcd < rr8 ? xcd * (qq + 1) : rr8 * (qq + 1) + (xcd - rr8) * qq) + (wg >> 3);
+    __shared__ __attribute__((aligned(16))) float smem[FilterLds<G>::FLOATS];
+    const int wgid = xcd_wgid();                 // block -> (query block, row split)
     const int nqb = a.nqb, nsplit = a.nsplit, dp = a.dp;
     if (wgid >= nqb * nsplit) return;
     float* const norm_base = smem + NS * STAGE;
@@ -245,25 +196,13 @@ knn_filter_tile_kernel(const FilterArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WQ;
-    const int wq = wave % WQ;
-    const int li = lane & 31;
-    const int lh = lane >> 5;
-    const int qcol = qb * BQ + wq * 32 + li;     // < nq_pad
+    const TileLanes<G> L(lane, wave);
+    const int wr = L.wr, lh = L.lh;
+    const int qcol = qb * BQ + L.wq * 32 + L.li; // < nq_pad
     const bool qvalid = qcol < a.nq;
     const int metric = a.metric;
     float qn = (metric == 1) ? a.qnorm[qcol] : 0.f;
     asm volatile("" : "+v"(qn));
-
-    const int prow = lane / CPR, pchk = lane % CPR;
-    // a piece's swizzled chunk offset depends on its place in the tile (piece parity), not on the
-    // row it holds: the swizzle goes through the source address
-    const int gsw0 = 4 * (pchk ^ (((0 * RPP + prow) / RPB) % CPR));
-    const int gsw1 = 4 * (pchk ^ (((1 * RPP + prow) / RPB) % CPR));
-    const int fsw = (li / RPB) % CPR;
-    int fo[CPR / 2];
-#pragma unroll
-    for (int c = 0; c < CPR / 2; ++c) fo[c] = li * BK + 4 * ((lh * (CPR / 2) + c) ^ fsw);
 
     float kd[KL];
     int ki[KL];
@@ -273,17 +212,11 @@ knn_filter_tile_kernel(const FilterArgs a) {
     const int nsteps = dp / BK;
     const float* qbase = a.qp + (size_t)qb * BQ * dp;
 
-    int64_t poff[LPW];          // query pieces: fixed; corpus pieces: re-derived per tile
-    bool pis_a[LPW];
-    uint32_t pdst[LPW];
+    // this lane's source of piece j (TileLanes).  Query pieces: fixed; corpus pieces: re-derived
+    // per tile from the list entry at the piece row's position
+    int64_t poff[LPW];
 #pragma unroll
-    for (int j = 0; j < LPW; ++j) {
-        const int pc = wave * LPW + j;
-        pis_a[j] = pc < PA;
-        const int prow0 = pis_a[j] ? pc * RPP : (pc - PA) * RPP;
-        poff[j] = (int64_t)(prow0 + prow) * dp + (((prow0 / RPP) & 1) ? gsw1 : gsw0);
-        pdst[j] = (uint32_t)(pis_a[j] ? pc * 256 : SA + (pc - PA) * 256) * 4u;
-    }
+    for (int j = 0; j < LPW; ++j) poff[j] = L.poff(j, dp);
     const uint32_t smem_u32 = lds_u32(smem);
     const uint32_t norm_u32 = lds_u32(norm_base);
     const uint32_t list_u32 = lds_u32(list_base);
@@ -304,12 +237,8 @@ knn_filter_tile_kernel(const FilterArgs a) {
         if (is == 0) {
             const uint32_t* ls = list_base + (it & 1) * BM;
 #pragma unroll
-            for (int j = 0; j < LPW; ++j) {
-                if (pis_a[j]) {
-                    const int pc = wave * LPW + j;
-                    poff[j] = (int64_t)ls[pc * RPP + prow] * dp + ((pc & 1) ? gsw1 : gsw0);
-                }
-            }
+            for (int j = 0; j < LPW; ++j)
+                if (L.is_a(j)) poff[j] = (int64_t)ls[L.prow(j)] * dp + L.psw(j);
             for (int jj = wave; jj < BM / 64; jj += NW)
                 dma4_norm(a.xnorm + ls[jj * 64 + lane],
                           norm_u32 + (uint32_t)((it % NS) * BM + jj * 64) * 4u);
@@ -317,7 +246,7 @@ knn_filter_tile_kernel(const FilterArgs a) {
         }
         const int k0 = is * BK;
 #pragma unroll
-        for (int j = 0; j < LPW; ++j) dma16((pis_a[j] ? a.xb : qbase) + poff[j] + k0, st + pdst[j]);
+        for (int j = 0; j < LPW; ++j) dma16((L.is_a(j) ? a.xb : qbase) + poff[j] + k0, st + L.pdst(j));
         if (++is == nsteps) { is = 0; ++it; }
         ibuf = (ibuf + 1 == NS) ? 0 : ibuf + 1;
     };
@@ -346,37 +275,10 @@ knn_filter_tile_kernel(const FilterArgs a) {
 
         for (int s = 0; s < nsteps; ++s) {
             --remaining;
-            if (remaining >= NS - 2) wait_vmcnt<LPW * (NS - 2)>();
-            else wait_vmcnt<0>();
-            barrier_lds();                       // everyone's DMA landed; previous stage read
-
+            tile_stage_wait<G>(remaining);
             const float* st = smem + cbuf * STAGE;
             cbuf = (cbuf + 1 == NS) ? 0 : cbuf + 1;
-            float av[WB][KH], bq[KH];
-            {
-                const float* bp = st + SA + wq * 32 * BK;
-#pragma unroll
-                for (int c = 0; c < CPR / 2; ++c) {
-                    const float4 v = *reinterpret_cast<const float4*>(bp + fo[c]);
-                    bq[4 * c] = v.x; bq[4 * c + 1] = v.y; bq[4 * c + 2] = v.z; bq[4 * c + 3] = v.w;
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < WB; ++b) {
-                const float* ap = st + (wr * RW + b * 32) * BK;
-#pragma unroll
-                for (int c = 0; c < CPR / 2; ++c) {
-                    const float4 v = *reinterpret_cast<const float4*>(ap + fo[c]);
-                    av[b][4 * c] = v.x; av[b][4 * c + 1] = v.y; av[b][4 * c + 2] = v.z; av[b][4 * c + 3] = v.w;
-                }
-            }
-            issue_next();                        // refills the buffer the previous stage used
-#pragma unroll
-            for (int kk = 0; kk < KH; ++kk) {
-#pragma unroll
-                for (int b = 0; b < WB; ++b)
-                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[b][kk], bq[kk], acc[b], 0, 0, 0);
-            }
+            tile_stage<G, kModeF32>(st, L, acc, issue_next);
         }
 
         // ---- epilogue.  The tile's norms landed before its first stage's barrier; their ring
@@ -386,10 +288,13 @@ knn_filter_tile_kernel(const FilterArgs a) {
 #pragma unroll
         for (int b = 0; b < WB; ++b) {
             float key[16];
-            unsigned mask = 0;
             const float tau = kd[KL - 1];
             const float tau_p = __shfl_xor(tau, 32, 64);       // the query's other rows' list
             const int rb = wr * RW + b * 32 + 4 * lh;          // position of accumulator reg 0
+            // tile_keys' loop with this kernel's test written in place: through the shared helper
+            // and a predicate the 128 x 128 tiles ran 0.5 - 0.75 % slower at a full mask
+            // (profiles/tile_core/README.md); the key formula itself is the shared tile_key
+            unsigned mask = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {                      // regs 4j..4j+3 = positions rb+8j+0..3
                 float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -398,14 +303,7 @@ knn_filter_tile_kernel(const FilterArgs a) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int r = 4 * j + i;
-                    const float ip = acc[b][r];
-                    float kv;
-                    if (metric == 1) {
-                        kv = fmaf(-2.f, ip, qn + nv[i]);
-                        kv = kv < 0.f ? 0.f : kv;
-                    } else {
-                        kv = -ip;
-                    }
+                    const float kv = tile_key(acc[b][r], qn, nv[i], metric);
                     key[r] = kv;
                     bool pass = qvalid && (pos0 + (uint32_t)(rb + 8 * j + i) < m);
                     // a NaN key fails the comparisons: never returned
@@ -456,44 +354,13 @@ knn_filter_tile_kernel(const FilterArgs a) {
     }
 }
 
-__global__ void filter_offsets_kernel(unsigned* off, int nseg, uint32_t seg) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= nseg) off[i] = (unsigned)i * seg;
-}
+// The tile plan (the row splits are planned from ntotal, an upper bound of the selected count)
+// and the candidate lists of the k <= KNN_MAX_K route.
+struct FilterPlan : TilePlan { int km, ncand; };
 
-// Row q of D / I from the first k sorted values of segment q (~0 = empty: past m, or a NaN key).
-__global__ void __launch_bounds__(256)
-filter_unpack_kernel(const uint64_t* __restrict__ sorted, uint32_t seg, int k, int metric,
-                     int64_t id_offset, float* __restrict__ D, int64_t* __restrict__ I) {
-    const int64_t q = blockIdx.y;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= k) return;
-    const uint64_t x = i < (int64_t)seg ? sorted[q * seg + i] : ~0ull;
-    if (x == ~0ull) {
-        D[q * k + i] = metric == 1 ? FLT_MAX : -FLT_MAX;
-        I[q * k + i] = -1;
-    } else {
-        const float key = key_from_ordered((uint32_t)(x >> 32));
-        D[q * k + i] = metric == 1 ? key : -key;
-        I[q * k + i] = (int64_t)(uint32_t)x + id_offset;
-    }
-}
-
-struct FilterPlan { int wr, wq, bk, bm, bq, nqb, nq_pad, nsplit, km, ncand; };
-
-// knn_range.hip's plan: one geometry per batch size, one stage depth per row stride.  The row
-// splits are planned from ntotal, an upper bound of the selected count.
 FilterPlan make_filter_plan(int64_t ntotal, int64_t nq, int k, int dp, int cus) {
     FilterPlan p{};
-    if (nq <= 32) { p.wr = 2; p.wq = 1; } else { p.wr = 1; p.wq = 4; }
-    p.bk = dp % 32 == 0 ? 32 : 16;
-    p.bm = p.wr * 128;
-    p.bq = p.wq * 32;
-    p.nqb = (int)((nq + p.bq - 1) / p.bq);
-    p.nq_pad = p.nqb * p.bq;
-    const int ntiles = (int)((ntotal + p.bm - 1) / p.bm);
-    const int target = cus * 2;
-    p.nsplit = std::max(1, std::min((target + p.nqb - 1) / p.nqb, ntiles));
+    static_cast<TilePlan&>(p) = make_tile_plan(ntotal, nq, dp, cus);
     p.km = k > KNN_MAX_K ? 0 : (k <= 16 ? 16 : 32);
     p.ncand = p.nsplit * p.wr * 2 * p.km;
     return p;
@@ -502,14 +369,10 @@ FilterPlan make_filter_plan(int64_t ntotal, int64_t nq, int k, int dp, int cus) 
 template <int KM>
 hipError_t launch_filter_tile_km(const FilterPlan& p, const FilterArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)(p.nqb * p.nsplit));
-#define IMGREC_FILTER_LAUNCH(WRV, WQV, NSV, BKV)                                                  \
-    hipLaunchKernelGGL((knn_filter_tile_kernel<WRV, WQV, NSV, BKV, KM>), grid, dim3(WRV * WQV * 64), 0, st, a)
-    // the rings of knn_range.hip's launches
-    if (p.wr == 2 && p.bk == 32) IMGREC_FILTER_LAUNCH(2, 1, 2, 32);
-    else if (p.wr == 2) IMGREC_FILTER_LAUNCH(2, 1, 3, 16);
-    else if (p.bk == 32) IMGREC_FILTER_LAUNCH(1, 4, 2, 32);
-    else IMGREC_FILTER_LAUNCH(1, 4, 2, 16);
-#undef IMGREC_FILTER_LAUNCH
+    with_tile_ring(p, [&](auto g) {
+        using G = decltype(g);
+        hipLaunchKernelGGL((knn_filter_tile_kernel<G::WR, G::WQ, G::NS, G::BK, KM>), grid, dim3(G::NT), 0, st, a);
+    });
     return hipGetLastError();
 }
 
@@ -521,7 +384,7 @@ hipError_t launch_filter_tile(const FilterPlan& p, const FilterArgs& a, hipStrea
 
 // keys of one any-k chunk: knn_hugek.hip's workspace cap (1 GiB of u64, twice for the sort)
 constexpr int64_t kFilterSortEntries = int64_t(1) << 27;
-constexpr int64_t kFilterSortMaxQ = 65535;         // the unpack grid's y extent
+constexpr int64_t kFilterSortMaxQ = 65535;         // the write grid's y extent
 
 int compact(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lmap, bool invert,
             hipStream_t st) {
@@ -609,14 +472,11 @@ int filtered_sorted(knn_index* ix, const float* q, int64_t nq, int k, float* D, 
         if ((rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
         KNN_HIP(launch_filter_tile(p, a, st));
         if (e1) KNN_HIP(hipEventRecord(e1, st));
-        hipLaunchKernelGGL(filter_offsets_kernel, dim3((unsigned)((cn + 256) / 256)), dim3(256), 0, st,
-                           ix->hk_off, (int)cn, (uint32_t)m_pad);
-        KNN_HIP(hipGetLastError());
-        KNN_HIP(sort_u64_segments(ix->hk_a, ix->hk_b, cn * m_pad, (int)cn, ix->hk_off, 64u, &ix->hk_tmp,
-                                  &ix->hk_tmp_cap, false, st));
-        hipLaunchKernelGGL(filter_unpack_kernel, dim3((unsigned)((k + 255) / 256), (unsigned)cn), dim3(256), 0,
-                           st, ix->hk_b, (uint32_t)m_pad, k, kmetric, ix->id_offset, D + c0 * k, I + c0 * k);
-        KNN_HIP(hipGetLastError());
+        // ~0 = empty (past m, or a NaN key): sorts last, written as a padding entry
+        KNN_HIP(sort_equal_segments(ix->hk_a, ix->hk_b, (int)cn, m_pad, 64u, ix->hk_off, &ix->hk_tmp,
+                                    &ix->hk_tmp_cap, false, st));
+        KNN_HIP(launch_sorted_write(ix->hk_b, m_pad, (int)cn, k, kmetric, 32, ix->id_offset, true, D + c0 * k,
+                                    I + c0 * k, st));
     }
     return KNN_OK;
 }

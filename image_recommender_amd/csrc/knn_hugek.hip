@@ -157,11 +157,10 @@ int bits_for(int64_t n) {                      // bits a row index < n needs
     return b;
 }
 
-// Segmented sort of nseg segments of `seg` u64 in `in` -> `out` over bits [0, end_bit).  The
-// sort's temporary storage grows in *tmp: by hipMalloc (an index's workspace), or in stream order
-// by hipMallocAsync when `async_tmp` (a merge's, freed by the caller with hipFreeAsync).
-hipError_t sort_segments(uint64_t* in, uint64_t* out, int nseg, int64_t seg, unsigned end_bit,
-                         unsigned* off, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st) {
+}  // namespace
+
+hipError_t sort_equal_segments(uint64_t* in, uint64_t* out, int nseg, int64_t seg, unsigned end_bit,
+                               unsigned* off, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st) {
     hipLaunchKernelGGL(hugek_offsets_kernel, dim3((unsigned)((nseg + 256) / 256)), dim3(256), 0, st, off,
                        nseg, seg);
     hipError_t e = hipGetLastError();
@@ -169,7 +168,12 @@ hipError_t sort_segments(uint64_t* in, uint64_t* out, int nseg, int64_t seg, uns
     return sort_u64_segments(in, out, (int64_t)nseg * seg, nseg, off, end_bit, tmp, tmp_cap, async_tmp, st);
 }
 
-}  // namespace
+hipError_t launch_sorted_write(const uint64_t* sorted, int64_t seg, int nq, int k, int metric, int rb,
+                               int64_t id_offset, bool label_is_row, float* D, int64_t* I, hipStream_t st) {
+    hipLaunchKernelGGL(hugek_write_kernel, dim3((unsigned)((k + 255) / 256), (unsigned)nq), dim3(256), 0, st,
+                       sorted, seg, k, metric, rb, id_offset, label_is_row, D, I);
+    return hipGetLastError();
+}
 
 hipError_t sort_u64_segments(uint64_t* in, uint64_t* out, int64_t total, int nseg, const unsigned* off,
                              unsigned end_bit, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st) {
@@ -218,11 +222,10 @@ int hugek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int
         hipLaunchKernelGGL(hugek_keys_kernel, grid, dim3(256), 0, st, ix->xb, ix->xn, N, ix->dp, ix->qpad,
                            ix->qnorm, (int)qc, kmetric, rb, ix->hk_a);
         KNN_HIP(hipGetLastError());
-        KNN_HIP(sort_segments(ix->hk_a, ix->hk_b, (int)qc, N, end_bit, ix->hk_off, &ix->hk_tmp,
-                              &ix->hk_tmp_cap, false, st));
-        hipLaunchKernelGGL(hugek_write_kernel, dim3((unsigned)((k + 255) / 256), (unsigned)qc), dim3(256), 0,
-                           st, ix->hk_b, N, k, kmetric, rb, ix->id_offset, true, D + q0 * k, I + q0 * k);
-        KNN_HIP(hipGetLastError());
+        KNN_HIP(sort_equal_segments(ix->hk_a, ix->hk_b, (int)qc, N, end_bit, ix->hk_off, &ix->hk_tmp,
+                                    &ix->hk_tmp_cap, false, st));
+        KNN_HIP(launch_sorted_write(ix->hk_b, N, (int)qc, k, kmetric, rb, ix->id_offset, true, D + q0 * k,
+                                    I + q0 * k, st));
     }
     return KNN_OK;
 }
@@ -264,10 +267,8 @@ hipError_t launch_merge_huge(const float* cD, const int64_t* cI, int nlists, int
         hipLaunchKernelGGL(hugek_pack_lists_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)qc), dim3(256), 0,
                            st, cD + q0 * kin, cI + q0 * kin, nlists, kin, sd, si, metric, a);
         if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = sort_segments(a, b, (int)qc, M, 64u, off, &tmp, &tmp_cap, true, st)) != hipSuccess) break;
-        hipLaunchKernelGGL(hugek_write_kernel, dim3((unsigned)((k + 255) / 256), (unsigned)qc), dim3(256), 0,
-                           st, b, M, k, metric, 32, (int64_t)0, false, D + q0 * k, I + q0 * k);
-        e = hipGetLastError();
+        if ((e = sort_equal_segments(a, b, (int)qc, M, 64u, off, &tmp, &tmp_cap, true, st)) != hipSuccess) break;
+        e = launch_sorted_write(b, M, (int)qc, k, metric, 32, (int64_t)0, false, D + q0 * k, I + q0 * k, st);
     }
     cleanup();
     return e;

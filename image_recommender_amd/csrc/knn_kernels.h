@@ -333,6 +333,15 @@ hipError_t launch_max_norm(const float* xn, int64_t n, float* out, hipStream_t s
 // on st when async_tmp)
 hipError_t sort_u64_segments(uint64_t* in, uint64_t* out, int64_t total, int nseg, const unsigned* off,
                              unsigned end_bit, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st);
+// the same for nseg equal segments of `seg` keys in `in` -> `out`: writes their offsets into `off`
+// (nseg + 1 entries) first.  The temporary storage grows by hipMalloc (an index's workspace), or in
+// stream order when `async_tmp` (a merge's, freed by the caller with hipFreeAsync)
+hipError_t sort_equal_segments(uint64_t* in, uint64_t* out, int nseg, int64_t seg, unsigned end_bit,
+                               unsigned* off, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st);
+// row q of D / I (k entries) from the first min(k, seg) sorted values (key bits << rb | label) of
+// segment q, padded past them and from the first ~0 (empty) value on; label_is_row adds id_offset
+hipError_t launch_sorted_write(const uint64_t* sorted, int64_t seg, int nq, int k, int metric, int rb,
+                               int64_t id_offset, bool label_is_row, float* D, int64_t* I, hipStream_t st);
 // IVF-PQ for any k: every probed row's ADC key, a segmented sort per query, the first k
 hipError_t launch_ivfpq_scan_all(const float* lut, const int64_t* probes, int64_t nq, int nprobe,
                                  const int64_t* list_off, const uint16_t* codes, const int64_t* ids,

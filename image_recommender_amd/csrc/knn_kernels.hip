@@ -32,20 +32,10 @@
 
 #include "knn_certify.h"
 #include "knn_kernels.h"
+#include "knn_tile.h"
 #include "wave_ops.h"
 
 namespace imgrec {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// 16-B fragment chunk c of a per-lane float array, reinterpreted as 8 bf16 (split layout)
-template <int N>
-__device__ __forceinline__ bf16x8 frag_bf16(const float (&v)[N], int c) {
-    const f32x4 f = {v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]};
-    return __builtin_bit_cast(bf16x8, f);
-}
 
 // ---------------------------------------------------------------------------------------------
 // helpers
@@ -114,112 +104,9 @@ rows_ingest_kernel(const float* __restrict__ src, int64_t n, int d, int dp, int6
 }
 
 // ---------------------------------------------------------------------------------------------
-// knn_tile_topk
-//
-// Workgroup = WR x WQ waves; wave tile = 32*WB corpus rows (WB MFMA row blocks, 4 or 8) x 32
-// queries, so the workgroup tile is BM = 32*WB*WR rows x BQ = 32*WQ queries.  A workgroup owns one query block and a
-// contiguous range of row tiles (a "row split") and streams it as one continuous sequence of
-// BK-deep K stages: (tile t0, stage 0..nsteps-1), (t0+1, 0..), ...
-//
-// Staging is LDS-DMA (global_load_lds_dwordx4): each wave instruction moves one 1-KiB piece
-// (RPP rows x 4*BK bytes) straight into LDS, no staging VGPRs, into an NS-deep ring; a stage is
-// read NS-1 iterations after its loads were issued, behind a counted `s_waitcnt vmcnt` and one raw
-// s_barrier per stage (cdna_hip_programming.md §5 "Pipelining across barriers").  The ring runs
-// across tile boundaries, so a tile's top-k epilogue overlaps the next tile's loads.
-//
-// LDS image: rows of BK floats; 16-B chunk c of row r stored at chunk c ^ ((r / RPB) % CPR)
-// (RPB = rows per 256-B bank row, CPR = chunks per row).  The XOR is applied to the per-lane
-// GLOBAL source address (the DMA destination is lane-linear); the fragment reads apply the same
-// XOR, which makes every ds_read_b128 16-lane group hit 16 distinct 16-B bank slots.
+// knn_tile_topk: the tile core of knn_tile.h (geometry, LDS image, stage consumer, key forming)
+// with contiguous row tiles and a per-lane register top-K list.
 // ---------------------------------------------------------------------------------------------
-template <int WR, int WQ, int NS, int BK, int WB = 4>
-struct TileGeom {
-    static constexpr int NW = WR * WQ, NT = NW * 64;
-    static constexpr int RW = 32 * WB;                 // corpus rows per wave
-    static constexpr int BM = WR * RW, BQ = WQ * 32;
-    static constexpr int CPR = BK / 4;                 // 16-B chunks per staged row
-    static constexpr int RPP = 64 / CPR;               // rows per 1-KiB DMA piece
-    static constexpr int RPB = 64 / BK;                // rows per 256-B bank row
-    static constexpr int SA = BM * BK, SB = BQ * BK, STAGE = SA + SB;   // floats
-    static constexpr int PA = BM / RPP, PB = BQ / RPP, PIECES = PA + PB;
-    static constexpr int LPW = PIECES / NW;            // pieces per wave per stage
-    // epilogue key parking in a spent stage: all 16 keys of a block in one round when they fit
-    static constexpr int PR = (SA + SB) >= NW * 16 * 64 ? 16 : 8;
-    static constexpr int PARK = NW * PR * 64;
-    static constexpr int LDS_FLOATS = NS * STAGE + NS * BM;
-    static_assert(BK == 16 || BK == 32, "stage depth");
-    static_assert(PIECES % NW == 0, "pieces must divide evenly over waves");
-    static_assert(BM % 64 == 0, "norm DMA uses whole waves");
-    static_assert(STAGE >= PARK, "epilogue parking must fit in one stage");
-    static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
-};
-
-// LDS byte address of a pointer into __shared__ memory.
-__device__ __forceinline__ uint32_t lds_addr(const float* p) {
-    return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) float*)p);
-}
-
-// LDS-DMA issued from inline asm (M0 = wave-uniform LDS destination, set and restored inside the
-// statement).  hipcc does not see these as LDS writes, so it inserts no vmcnt(0) in front of the
-// fragment ds_reads (it would for __builtin_amdgcn_global_load_lds, serialising the ring); every
-// wait on them is the explicit counted wait_vmcnt below.
-__device__ __forceinline__ void dma16(const float* g, uint32_t lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
-}
-// The same with the non-temporal policy, for bf16 corpus rows that exactly one workgroup reads (a
-// launch with one query block): nq = 1 on 1M x 1968 0.695 -> 0.667 ms.  The fp32 corpus of the
-// exact kernel runs slower with it (1.94 -> 2.70 ms), so it keeps the default policy.
-__device__ __forceinline__ void dma16_nt(const float* g, uint32_t lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
-}
-__device__ __forceinline__ void dma4(const float* g, uint32_t lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
-
-// s_barrier that also orders the compiler's LDS accesses (the intrinsic alone is IntrNoMem).
-__device__ __forceinline__ void barrier_raw() {
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-// Insert into an ascending list when labels reach this lane in increasing order (true inside
-// the fused kernel: a lane visits its rows in increasing row order), so "ranks before" is a plain
-// key comparison and an equal key always lands behind the existing entries.
-template <int K>
-__device__ __forceinline__ void list_insert_mono(float (&kd)[K], int (&ki)[K], float d, int id) {
-    // c[p]: d goes before slot p of the old list (monotone); one compare, four selects per slot
-    bool c[K];
-#pragma unroll
-    for (int p = 0; p < K; ++p) c[p] = d < kd[p];
-#pragma unroll
-    for (int p = K - 1; p > 0; --p) {
-        // the same select on an ascending list is the median of (kd[p-1], d, kd[p]): one v_med3
-        kd[p] = __builtin_amdgcn_fmed3f(kd[p - 1], d, kd[p]);
-        ki[p] = c[p - 1] ? ki[p - 1] : (c[p] ? id : ki[p]);
-    }
-    kd[0] = c[0] ? d : kd[0];
-    ki[0] = c[0] ? id : ki[0];
-}
-
-// 4-wave workgroups run two per CU (two waves per SIMD): hold them to 256 VGPR+AGPR per lane.
-#define IMGREC_MIN_WAVES(nw) ((nw) == 4 ? 2 : 1)
 // The work of one (query block, row split) item `wgid` (query block wgid % nqb, split
 // wgid / nqb), in the LDS array smem (G::LDS_FLOATS floats).  The kernel below runs one item per
 // workgroup; the certificate tail kernel loops over the items of a device-planned exact re-run.
@@ -230,10 +117,8 @@ __device__ __forceinline__ void tile_topk_item(
         int ntiles, int nsplit, int nqb, int64_t id_offset, float* __restrict__ cand_d,
         int64_t* __restrict__ cand_i, int ncand, int wgid, float* __restrict__ smem) {
     using G = TileGeom<WR, WQ, NS, BK, WB>;
-    constexpr int RW = G::RW;
-    constexpr int NW = G::NW, BM = G::BM, BQ = G::BQ, SA = G::SA, STAGE = G::STAGE;
-    constexpr int PA = G::PA, LPW = G::LPW, CPR = G::CPR, RPP = G::RPP, RPB = G::RPB, PR = G::PR;
-    constexpr int KH = BK / 2;          // MFMA sub-steps per stage (each covers depth 2)
+    constexpr int RW = G::RW, NW = G::NW, BM = G::BM, BQ = G::BQ, STAGE = G::STAGE;
+    constexpr int LPW = G::LPW, PR = G::PR;
     float* const norm_base = smem + NS * STAGE;
     const int qb = wgid % nqb;
     const int split = wgid / nqb;
@@ -248,25 +133,12 @@ __device__ __forceinline__ void tile_topk_item(
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WQ;
-    const int wq = wave % WQ;
-    const int li = lane & 31;
-    const int lh = lane >> 5;
-    const int qcol = qb * BQ + wq * 32 + li;     // the query this lane owns (< nq_pad)
+    const TileLanes<G> L(lane, wave);
+    const int wr = L.wr, lh = L.lh;
+    const int qcol = qb * BQ + L.wq * 32 + L.li; // the query this lane owns (< nq_pad)
     const bool qvalid = qcol < nq;
     float qn = (metric == 1) ? qnorm[qcol] : 0.f;
     asm volatile("" : "+v"(qn));   // consume the load here, before the DMA stream starts
-
-    // per-lane DMA source offsets inside a piece (row lane/CPR, logical chunk swizzled); the
-    // swizzle of a piece's rows depends on the piece index modulo 64/(RPP*...) -> two variants.
-    const int prow = lane / CPR, pchk = lane % CPR;
-    const int goff0 = prow * dp + 4 * (pchk ^ (((0 * RPP + prow) / RPB) % CPR));
-    const int goff1 = prow * dp + 4 * (pchk ^ (((1 * RPP + prow) / RPB) % CPR));
-    // per-lane fragment offsets inside a 32-row block: logical chunks lh*CPR/2 + c of row li
-    const int fsw = (li / RPB) % CPR;
-    int fo[CPR / 2];
-#pragma unroll
-    for (int c = 0; c < CPR / 2; ++c) fo[c] = li * BK + 4 * ((lh * (CPR / 2) + c) ^ fsw);
 
     float kd[KM];
     int ki[KM];
@@ -277,23 +149,17 @@ __device__ __forceinline__ void tile_topk_item(
     const float* qbase = qp + (size_t)qb * BQ * dp;
 
     // ---- DMA issue cursor (runs NS-1 stages ahead of the consumer) -------------------------
-    // Piece j of this wave is piece pc = wave*LPW + j of a stage: an A piece (RPP corpus rows of
-    // the tile) or a B piece (RPP queries).  Its source is base + tile offset + BK*stage floats.
+    // The source of this lane's 16 B of piece j (TileLanes) is base + tile offset + poff[j] +
+    // BK*stage floats.
     int64_t poff[LPW];
-    bool pis_a[LPW];
-    uint32_t pdst[LPW];
     bool pnt[LPW];                          // corpus piece of a one-query-block launch: read once
 #pragma unroll
     for (int j = 0; j < LPW; ++j) {
-        const int pc = wave * LPW + j;
-        pis_a[j] = pc < PA;
-        pnt[j] = MODE == kModeBF16 && pis_a[j] && nqb == 1;   // fp32 rows: 1.94 -> 2.70 ms at nq = 1
-        const int prow0 = pis_a[j] ? pc * RPP : (pc - PA) * RPP;
-        poff[j] = (int64_t)prow0 * dp + (((prow0 / RPP) & 1) ? goff1 : goff0);
-        pdst[j] = (uint32_t)(pis_a[j] ? pc * 256 : SA + (pc - PA) * 256) * 4u;
+        pnt[j] = MODE == kModeBF16 && L.is_a(j) && nqb == 1;   // fp32 rows: 1.94 -> 2.70 ms at nq = 1
+        poff[j] = L.poff(j, dp);
     }
-    const uint32_t smem_u32 = lds_addr(smem);
-    const uint32_t norm_u32 = lds_addr(norm_base);
+    const uint32_t smem_u32 = lds_u32(smem);
+    const uint32_t norm_u32 = lds_u32(norm_base);
     int it = t0, is = 0, ibuf = 0;
     const float* itile = xb + (size_t)tile(t0) * BM * dp;   // corpus rows of tile `it`
     auto issue_next = [&]() __attribute__((always_inline)) {
@@ -301,14 +167,14 @@ __device__ __forceinline__ void tile_topk_item(
         const uint32_t st = smem_u32 + (uint32_t)(ibuf * STAGE) * 4u;
         if (is == 0) {                      // row norms of the tile, one 4-B DMA per lane
             for (int j = wave; j < BM / 64; j += NW)
-                dma4(xnorm + (size_t)tile(it) * BM + j * 64 + lane,
-                     norm_u32 + (uint32_t)(((it - t0) % NS) * BM + j * 64) * 4u);
+                dma4_norm(xnorm + (size_t)tile(it) * BM + j * 64 + lane,
+                          norm_u32 + (uint32_t)(((it - t0) % NS) * BM + j * 64) * 4u);
         }
         const int k0 = is * BK;
 #pragma unroll
         for (int j = 0; j < LPW; ++j) {
-            if (pnt[j]) dma16_nt(itile + poff[j] + k0, st + pdst[j]);
-            else dma16((pis_a[j] ? itile : qbase) + poff[j] + k0, st + pdst[j]);
+            if (pnt[j]) dma16_nt(itile + poff[j] + k0, st + L.pdst(j));
+            else dma16((L.is_a(j) ? itile : qbase) + poff[j] + k0, st + L.pdst(j));
         }
         if (++is == nsteps) { is = 0; ++it; itile += (size_t)nsplit * BM * dp; }
         ibuf = (ibuf + 1 == NS) ? 0 : ibuf + 1;
@@ -327,115 +193,33 @@ __device__ __forceinline__ void tile_topk_item(
 
         const float* st = smem;
         for (int s = 0; s < nsteps; ++s) {
-            // own DMA of this stage landed (later stages may stay in flight)
-            --remaining;                             // stages issued after this one: min(NS-2, remaining)
-            if (remaining >= NS - 2) wait_vmcnt<LPW * (NS - 2)>();
-            else if (NS > 3 && remaining == 1) wait_vmcnt<LPW>();
-            else wait_vmcnt<0>();
-            barrier_raw();                           // everyone's DMA landed; previous stage read
-
+            --remaining;
+            tile_stage_wait<G>(remaining);
             st = smem + cbuf * STAGE;
             cbuf = (cbuf + 1 == NS) ? 0 : cbuf + 1;
-            float a[WB][KH], bq[KH];
-            {
-                const float* bp = st + SA + wq * 32 * BK;
-#pragma unroll
-                for (int c = 0; c < CPR / 2; ++c) {
-                    const float4 v = *reinterpret_cast<const float4*>(bp + fo[c]);
-                    bq[4 * c] = v.x; bq[4 * c + 1] = v.y; bq[4 * c + 2] = v.z; bq[4 * c + 3] = v.w;
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < WB; ++b) {
-                const float* ap = st + (wr * RW + b * 32) * BK;
-#pragma unroll
-                for (int c = 0; c < CPR / 2; ++c) {
-                    const float4 v = *reinterpret_cast<const float4*>(ap + fo[c]);
-                    a[b][4 * c] = v.x; a[b][4 * c + 1] = v.y; a[b][4 * c + 2] = v.z; a[b][4 * c + 3] = v.w;
-                }
-            }
-            // The stage's DMA pieces go out right after the fragment reads (their address math
-            // overlaps the LDS latency), before the MFMAs.  Measured alternatives, all slower:
-            // pieces pinned between MFMAs (38.6 ms vs 33.5 at BK=16), staggered per wave (38.8),
-            // a 5-deep ring (39.0).
-            issue_next();                            // refills the buffer the previous stage used
-            if constexpr (MODE == kModeBF16) {
-                // bf16 rows (2 elements per 32-bit word): this lane half's chunk c holds the 8
-                // elements of MFMA k-step c (depth 32h + 8c + 0..7 of the 64-deep stage, the same
-                // permutation on both operands); one bf16 MFMA per product
-#pragma unroll
-                for (int c = 0; c < CPR / 2; ++c) {
-                    const bf16x8 bv = frag_bf16(bq, c);
-#pragma unroll
-                    for (int b = 0; b < WB; ++b)
-                        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_bf16(a[b], c), bv, acc[b], 0, 0, 0);
-                }
-            } else if constexpr (MODE == kModeSplit) {
-                // split layout: this lane half's chunks 2s / 2s+1 are the hi / lo bf16 planes of
-                // MFMA k-step s; dot ~= hi.hi + hi.lo + lo.hi (the lo.lo term is below the bound)
-#pragma unroll
-                for (int s2 = 0; s2 < CPR / 4; ++s2) {
-                    const bf16x8 bh = frag_bf16(bq, 2 * s2), bl = frag_bf16(bq, 2 * s2 + 1);
-#pragma unroll
-                    for (int b = 0; b < WB; ++b)
-                        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_bf16(a[b], 2 * s2), bh, acc[b], 0, 0, 0);
-#pragma unroll
-                    for (int b = 0; b < WB; ++b)
-                        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_bf16(a[b], 2 * s2), bl, acc[b], 0, 0, 0);
-#pragma unroll
-                    for (int b = 0; b < WB; ++b)
-                        acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_bf16(a[b], 2 * s2 + 1), bh, acc[b], 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int kk = 0; kk < KH; ++kk) {
-#pragma unroll
-                    for (int b = 0; b < WB; ++b)
-                        acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[b][kk], bq[kk], acc[b], 0, 0, 0);
-                }
-            }
+            tile_stage<G, MODE>(st, L, acc, issue_next);
         }
 
-        // ---- epilogue: key = L2 distance (faiss exhaustive_L2sqr_blas form, clamped at 0) or
-        // -ip; screened against this lane's K-th key and (<=) its partner lane's K-th key (the
-        // partner holds the same query's other rows: a key worse than the partner's K-th cannot
-        // reach the union's top K).  Survivors are parked in the stage this tile just consumed
-        // (refilled only after the next barrier, which every wave reaches after its epilogue)
-        // and inserted one by one.
+        // ---- epilogue: each key (tile_keys) is screened against this lane's K-th key and (<=) its
+        // partner lane's K-th key (the partner holds the same query's other rows: a key worse
+        // than the partner's K-th cannot reach the union's top K).  Survivors are parked in the
+        // stage this tile just consumed (refilled only after the next barrier, which every wave
+        // reaches after its epilogue) and inserted one by one.
         // every wave (all lanes: qvalid is per lane) passes this barrier exactly once per tile
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        barrier_raw();                               // all fragment reads of the spent stage done
+        barrier_lds();                               // all fragment reads of the spent stage done
         if (qvalid) {
             const float* nrm = norm_base + ((t - t0) % NS) * BM;
             float* park = const_cast<float*>(st) + wave * (PR * 64);
 #pragma unroll
             for (int b = 0; b < WB; ++b) {
                 float key[16];
-                unsigned mask = 0;
                 const float tau = kd[KM - 1];
                 const float tau_p = __shfl_xor(tau, 32, 64);
                 const int rb = wr * RW + b * 32 + 4 * lh;      // row of accumulator reg 0
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {                  // regs 4j..4j+3 = rows rb+8j+0..3
-                    float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (metric == 1) n4 = *reinterpret_cast<const float4*>(nrm + rb + 8 * j);
-                    const float nv[4] = {n4.x, n4.y, n4.z, n4.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int r = 4 * j + i;
-                        const float ip = acc[b][r];
-                        float kv;
-                        if (metric == 1) {
-                            kv = fmaf(-2.f, ip, qn + nv[i]);
-                            kv = kv < 0.f ? 0.f : kv;
-                        } else {
-                            kv = -ip;
-                        }
-                        key[r] = kv;
-                        const bool pass = (row0 + rb + 8 * j + i < nrows) && kv < tau && kv <= tau_p;
-                        mask |= (unsigned)pass << r;
-                    }
-                }
+                const unsigned mask = tile_keys(acc[b], nrm, rb, metric, qn, key, [&](int off, float kv) __attribute__((always_inline)) {
+                    return (row0 + rb + off < nrows) && kv < tau && kv <= tau_p;
+                });
                 // survivors are inserted one per iteration per lane (ctz walk of the lane's own
                 // mask): the wave loops max-popcount times, not once per row any lane needs
 #pragma unroll
@@ -471,19 +255,14 @@ __device__ __forceinline__ void tile_topk_item(
 }
 
 template <int WR, int WQ, int KM, int NS, int BK, int MODE, int WB>
-__global__ void __launch_bounds__(WR * WQ * 64, IMGREC_MIN_WAVES(WR * WQ))
+__global__ void __launch_bounds__(WR * WQ * 64, (TileGeom<WR, WQ, NS, BK, WB>::MIN_WAVES))
 knn_tile_topk_kernel(const float* __restrict__ xb, const float* __restrict__ xnorm, int nrows,
                      int dp, const float* __restrict__ qp, const float* __restrict__ qnorm, int nq,
                      int metric, int ntiles, int nsplit, int nqb, int64_t id_offset,
                      float* __restrict__ cand_d, int64_t* __restrict__ cand_i, int ncand) {
     using G = TileGeom<WR, WQ, NS, BK, WB>;
     __shared__ __attribute__((aligned(16))) float smem[G::LDS_FLOATS];
-    // XCD-aware, bijective block -> (query block, row split) map: blocks b and b+8 share an XCD;
-    // consecutive remapped ids (same XCD) share a row split, so the corpus stages they stream are
-    // served from that XCD's L2 for all query blocks.
-    const int nwg = gridDim.x, wg = blockIdx.x;
-    const int xcd = wg & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int wgid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (wg >> 3);
+    const int wgid = xcd_wgid();                 // block -> (query block, row split)
     if (wgid >= nqb * nsplit) return;
     tile_topk_item<WR, WQ, KM, NS, BK, MODE, WB>(xb, xnorm, nrows, dp, qp, qnorm, nq, metric,
                                                  ntiles, nsplit, nqb, id_offset, cand_d, cand_i,

@@ -2,9 +2,9 @@
 // each query, in one pass over the corpus that writes only what passes.
 //
 // Pipeline of one query chunk (range_search_locked):
-//   1. knn_range_tile_kernel: the exact fp32 contraction of knn_kernels.hip's tile kernel
-//      (v_mfma_f32_32x32x2_f32, LDS-DMA ring) with its own stage loop; the epilogue forms the key
-//      ((|q|^2 + |x|^2) - 2 q.x clamped at 0, or -q.x), tests `key < r` (r = -radius for IP) and
+//   1. knn_range_tile_kernel: the exact fp32 contraction and key forming of the tile core
+//      (knn_tile.h: v_mfma_f32_32x32x2_f32, LDS-DMA ring; key (|q|^2 + |x|^2) - 2 q.x clamped at 0,
+//      or -q.x) over contiguous row tiles; the epilogue tests `key < r` (r = -radius for IP) and
 //      appends the survivors to a buffer: per 32-row block a wave counts its lanes' survivors,
 //      reserves their slots with ONE returning agent-scope atomic and every lane stores its
 //      (key bits << 32 | row, query) entries with plain stores.  Per-query hit counts are kept in
@@ -33,47 +33,11 @@
 #include <vector>
 
 #include "knn_index.h"
-#include "lds_dma.h"
+#include "knn_tile.h"
 #include "wave_ops.h"
 
 namespace imgrec {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// The tile geometry of knn_kernels.hip (TileGeom) without the top-k epilogue's key parking:
-// WR x WQ waves of 128 rows x 32 queries, BK-deep stages in an NS ring.
-template <int WR, int WQ, int NS, int BK>
-struct RangeGeom {
-    static constexpr int WB = 4;
-    static constexpr int NW = WR * WQ, NT = NW * 64;
-    static constexpr int RW = 32 * WB;
-    static constexpr int BM = WR * RW, BQ = WQ * 32;
-    static constexpr int CPR = BK / 4;                 // 16-B chunks per staged row
-    static constexpr int RPP = 64 / CPR;               // rows per 1-KiB DMA piece
-    static constexpr int RPB = 64 / BK;                // rows per 256-B bank row
-    static constexpr int SA = BM * BK, SB = BQ * BK, STAGE = SA + SB;   // floats
-    static constexpr int PA = BM / RPP, PB = BQ / RPP, PIECES = PA + PB;
-    static constexpr int LPW = PIECES / NW;
-    static constexpr int LDS_FLOATS = NS * STAGE + NS * BM;
-    static_assert(BK == 16 || BK == 32, "stage depth");
-    static_assert(PIECES % NW == 0, "pieces must divide evenly over waves");
-    static_assert(BM % 64 == 0, "norm DMA uses whole waves");
-    static_assert(LDS_FLOATS * 4 <= 160 * 1024, "LDS budget");
-};
-
-__device__ __forceinline__ void dma16(const float* g, uint32_t lds) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
-}
 
 struct RangeArgs {
     const float* xb;            // corpus, rows padded to 256, stride dp
@@ -93,19 +57,13 @@ struct RangeArgs {
 };
 
 template <int WR, int WQ, int NS, int BK>
-__global__ void __launch_bounds__(WR * WQ * 64, WR * WQ == 4 ? 2 : 1)
+__global__ void __launch_bounds__(WR * WQ * 64, (TileGeom<WR, WQ, NS, BK>::MIN_WAVES))
 knn_range_tile_kernel(const RangeArgs a) {
-    using G = RangeGeom<WR, WQ, NS, BK>;
-    constexpr int WB = G::WB, RW = G::RW;
-    constexpr int NW = G::NW, BM = G::BM, BQ = G::BQ, SA = G::SA, STAGE = G::STAGE;
-    constexpr int PA = G::PA, LPW = G::LPW, CPR = G::CPR, RPP = G::RPP, RPB = G::RPB;
-    constexpr int KH = BK / 2;
+    using G = TileGeom<WR, WQ, NS, BK>;
+    constexpr int WB = G::WB, RW = G::RW, NW = G::NW, BM = G::BM, BQ = G::BQ, STAGE = G::STAGE;
+    constexpr int LPW = G::LPW;
     __shared__ __attribute__((aligned(16))) float smem[G::LDS_FLOATS];
-    // XCD-aware block -> (query block, row split) map of the exact kernel: the workgroups of one
-    // XCD share row splits, so the corpus stages they stream come from that XCD's L2
-    const int nwg = gridDim.x, wg = blockIdx.x;
-    const int xcd = wg & 7, qq = nwg >> 3, rr8 = nwg & 7;
-    const int wgid = (xcd < rr8 ? xcd * (qq + 1) : rr8 * (qq + 1) + (xcd - rr8) * qq) + (wg >> 3);
+    const int wgid = xcd_wgid();                 // block -> (query block, row split)
     const int nqb = a.nqb, nsplit = a.nsplit, dp = a.dp;
     if (wgid >= nqb * nsplit) return;
     float* const norm_base = smem + NS * STAGE;
@@ -117,39 +75,21 @@ knn_range_tile_kernel(const RangeArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WQ;
-    const int wq = wave % WQ;
-    const int li = lane & 31;
-    const int lh = lane >> 5;
-    const int qcol = qb * BQ + wq * 32 + li;     // < nq_pad
+    const TileLanes<G> L(lane, wave);
+    const int wr = L.wr, lh = L.lh;
+    const int qcol = qb * BQ + L.wq * 32 + L.li; // < nq_pad
     const bool qvalid = qcol < a.nq;
     const int metric = a.metric;
     const float rad = a.r;
     float qn = (metric == 1) ? a.qnorm[qcol] : 0.f;
     asm volatile("" : "+v"(qn));
 
-    const int prow = lane / CPR, pchk = lane % CPR;
-    const int goff0 = prow * dp + 4 * (pchk ^ (((0 * RPP + prow) / RPB) % CPR));
-    const int goff1 = prow * dp + 4 * (pchk ^ (((1 * RPP + prow) / RPB) % CPR));
-    const int fsw = (li / RPB) % CPR;
-    int fo[CPR / 2];
-#pragma unroll
-    for (int c = 0; c < CPR / 2; ++c) fo[c] = li * BK + 4 * ((lh * (CPR / 2) + c) ^ fsw);
-
     const int nsteps = dp / BK;
     const float* qbase = a.qp + (size_t)qb * BQ * dp;
 
-    int64_t poff[LPW];
-    bool pis_a[LPW];
-    uint32_t pdst[LPW];
+    int64_t poff[LPW];                           // this lane's source of piece j (TileLanes)
 #pragma unroll
-    for (int j = 0; j < LPW; ++j) {
-        const int pc = wave * LPW + j;
-        pis_a[j] = pc < PA;
-        const int prow0 = pis_a[j] ? pc * RPP : (pc - PA) * RPP;
-        poff[j] = (int64_t)prow0 * dp + (((prow0 / RPP) & 1) ? goff1 : goff0);
-        pdst[j] = (uint32_t)(pis_a[j] ? pc * 256 : SA + (pc - PA) * 256) * 4u;
-    }
+    for (int j = 0; j < LPW; ++j) poff[j] = L.poff(j, dp);
     const uint32_t smem_u32 = lds_u32(smem);
     const uint32_t norm_u32 = lds_u32(norm_base);
     int it = 0, is = 0, ibuf = 0;
@@ -164,7 +104,7 @@ knn_range_tile_kernel(const RangeArgs a) {
         }
         const int k0 = is * BK;
 #pragma unroll
-        for (int j = 0; j < LPW; ++j) dma16((pis_a[j] ? itile : qbase) + poff[j] + k0, st + pdst[j]);
+        for (int j = 0; j < LPW; ++j) dma16((L.is_a(j) ? itile : qbase) + poff[j] + k0, st + L.pdst(j));
         if (++is == nsteps) { is = 0; ++it; itile += (size_t)nsplit * BM * dp; }
         ibuf = (ibuf + 1 == NS) ? 0 : ibuf + 1;
     };
@@ -183,37 +123,10 @@ knn_range_tile_kernel(const RangeArgs a) {
 
         for (int s = 0; s < nsteps; ++s) {
             --remaining;
-            if (remaining >= NS - 2) wait_vmcnt<LPW * (NS - 2)>();
-            else wait_vmcnt<0>();
-            barrier_lds();                       // everyone's DMA landed; previous stage read
-
+            tile_stage_wait<G>(remaining);
             const float* st = smem + cbuf * STAGE;
             cbuf = (cbuf + 1 == NS) ? 0 : cbuf + 1;
-            float av[WB][KH], bq[KH];
-            {
-                const float* bp = st + SA + wq * 32 * BK;
-#pragma unroll
-                for (int c = 0; c < CPR / 2; ++c) {
-                    const float4 v = *reinterpret_cast<const float4*>(bp + fo[c]);
-                    bq[4 * c] = v.x; bq[4 * c + 1] = v.y; bq[4 * c + 2] = v.z; bq[4 * c + 3] = v.w;
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < WB; ++b) {
-                const float* ap = st + (wr * RW + b * 32) * BK;
-#pragma unroll
-                for (int c = 0; c < CPR / 2; ++c) {
-                    const float4 v = *reinterpret_cast<const float4*>(ap + fo[c]);
-                    av[b][4 * c] = v.x; av[b][4 * c + 1] = v.y; av[b][4 * c + 2] = v.z; av[b][4 * c + 3] = v.w;
-                }
-            }
-            issue_next();                        // refills the buffer the previous stage used
-#pragma unroll
-            for (int kk = 0; kk < KH; ++kk) {
-#pragma unroll
-                for (int b = 0; b < WB; ++b)
-                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[b][kk], bq[kk], acc[b], 0, 0, 0);
-            }
+            tile_stage<G, kModeF32>(st, L, acc, issue_next);
         }
 
         // ---- epilogue: threshold and append.  The tile's norms landed before its first stage's
@@ -223,30 +136,10 @@ knn_range_tile_kernel(const RangeArgs a) {
 #pragma unroll
         for (int b = 0; b < WB; ++b) {
             float key[16];
-            unsigned mask = 0;
             const int rb = wr * RW + b * 32 + 4 * lh;          // row of accumulator reg 0
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {                      // regs 4j..4j+3 = rows rb+8j+0..3
-                float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (metric == 1) n4 = *reinterpret_cast<const float4*>(nrm + rb + 8 * j);
-                const float nv[4] = {n4.x, n4.y, n4.z, n4.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int r = 4 * j + i;
-                    const float ip = acc[b][r];
-                    float kv;
-                    if (metric == 1) {
-                        kv = fmaf(-2.f, ip, qn + nv[i]);
-                        kv = kv < 0.f ? 0.f : kv;
-                    } else {
-                        kv = -ip;
-                    }
-                    key[r] = kv;
-                    // a NaN key fails the comparison: never returned
-                    const bool pass = qvalid && (row0 + (uint32_t)(rb + 8 * j + i) < a.nrows) && kv < rad;
-                    mask |= (unsigned)pass << r;
-                }
-            }
+            const unsigned mask = tile_keys(acc[b], nrm, rb, metric, qn, key, [&](int off, float kv) __attribute__((always_inline)) {
+                return qvalid && (row0 + (uint32_t)(rb + off) < a.nrows) && kv < rad;
+            });
             if (__any(mask != 0)) {                            // wave-uniform: all lanes inside
                 const int cnt = __popc(mask);
                 const int ex = wave_excl_scan_i32(cnt);
@@ -345,34 +238,12 @@ range_unpack_kernel(const uint64_t* __restrict__ sorted, int64_t total, int metr
     I[e] = (int64_t)(uint32_t)x + id_offset;
 }
 
-struct RangePlan { int wr, wq, bk, bm, bq, nqb, nq_pad, ntiles, nsplit; };
-
-// One geometry per batch size, one stage depth per row stride (the depth order of the keys).
-RangePlan make_range_plan(int64_t ntotal, int64_t nq, int dp, int cus) {
-    RangePlan p{};
-    if (nq <= 32) { p.wr = 2; p.wq = 1; } else { p.wr = 1; p.wq = 4; }
-    p.bk = dp % 32 == 0 ? 32 : 16;
-    p.bm = p.wr * 128;
-    p.bq = p.wq * 32;
-    p.nqb = (int)((nq + p.bq - 1) / p.bq);
-    p.nq_pad = p.nqb * p.bq;
-    p.ntiles = (int)((ntotal + p.bm - 1) / p.bm);
-    const int target = cus * 2;
-    p.nsplit = std::max(1, std::min((target + p.nqb - 1) / p.nqb, p.ntiles));
-    return p;
-}
-
-hipError_t launch_range_tile(const RangePlan& p, const RangeArgs& a, hipStream_t st) {
+hipError_t launch_range_tile(const TilePlan& p, const RangeArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)(p.nqb * p.nsplit));
-#define IMGREC_RANGE_LAUNCH(WRV, WQV, NSV, BKV)                                                   \
-    hipLaunchKernelGGL((knn_range_tile_kernel<WRV, WQV, NSV, BKV>), grid, dim3(WRV * WQV * 64), 0, st, a)
-    // 2-slot rings at 32-deep stages: 74 / 66 KiB of LDS, so two workgroups share a CU (a 3-slot
-    // ring of the 256 x 32 tile leaves one 2-wave workgroup, half the SIMDs, per CU)
-    if (p.wr == 2 && p.bk == 32) IMGREC_RANGE_LAUNCH(2, 1, 2, 32);
-    else if (p.wr == 2) IMGREC_RANGE_LAUNCH(2, 1, 3, 16);
-    else if (p.bk == 32) IMGREC_RANGE_LAUNCH(1, 4, 2, 32);
-    else IMGREC_RANGE_LAUNCH(1, 4, 2, 16);
-#undef IMGREC_RANGE_LAUNCH
+    with_tile_ring(p, [&](auto g) {
+        using G = decltype(g);
+        hipLaunchKernelGGL((knn_range_tile_kernel<G::WR, G::WQ, G::NS, G::BK>), grid, dim3(G::NT), 0, st, a);
+    });
     return hipGetLastError();
 }
 
@@ -405,7 +276,7 @@ int range_chunks(knn_index* ix, const float* q, int64_t nq, float radius, hipStr
     int64_t base = 0;
     for (int64_t c0 = 0; c0 < nq; c0 += kQueryChunk) {
         const int64_t cn = std::min(kQueryChunk, nq - c0);
-        const RangePlan p = make_range_plan(ix->ntotal, cn, ix->dp, ix->cus);
+        const TilePlan p = make_tile_plan(ix->ntotal, cn, ix->dp, ix->cus);
         if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
         if ((rc = grow(&ix->qnorm, &ix->qnorm_cap, (size_t)p.nq_pad)) != KNN_OK) return rc;
         if ((rc = grow(&ix->rg_cnt, &ix->rg_cnt_cap, (size_t)cn)) != KNN_OK) return rc;

@@ -1,9 +1,11 @@
-// lds_dma.h — global -> LDS DMA helpers shared by the 256 x 256-tile bf16 kernels
-// (knn_b16w.hip: the k-NN candidate pass; vit_gemm.hip: the ViT GEMMs).
+// lds_dma.h — global -> LDS DMA helpers shared by every kernel that stages through an LDS-DMA ring
+// (knn_tile.h: the fp32 tile core of the top-k, range and filter kernels; knn_b16w.hip: the bf16
+// candidate pass; vit_gemm.hip: the ViT GEMMs).
 //
-// global_load_lds_dwordx4 is issued from inline asm with M0 set and restored inside the same
-// statement: the builtin makes hipcc insert a vmcnt(0) before every later LDS read, which would
-// serialise the ring (DESIGN.md "Kernels").
+// LDS-DMA is issued from inline asm (M0 = wave-uniform LDS destination, set and restored inside the
+// statement).  hipcc does not see these as LDS writes, so it inserts no vmcnt(0) in front of the
+// fragment ds_reads (it would for __builtin_amdgcn_global_load_lds, serialising the ring: DESIGN.md
+// "Kernels"); every wait on them is the explicit counted wait_vmcnt below.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +15,25 @@ namespace imgrec {
 
 __device__ __forceinline__ uint32_t lds_u32(const void* p) {
     return (uint32_t)(uintptr_t)((const __attribute__((address_space(3))) char*)p);
+}
+
+// One 1-KiB piece: 16 B per lane, lane-linear in LDS.
+__device__ __forceinline__ void dma16(const float* g, uint32_t lds) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
+}
+// The same with the non-temporal policy, for bf16 corpus rows that exactly one workgroup reads (a
+// launch with one query block): nq = 1 on 1M x 1968 0.695 -> 0.667 ms.  The fp32 corpus of the
+// exact kernel runs slower with it (1.94 -> 2.70 ms), so it keeps the default policy.
+__device__ __forceinline__ void dma16_nt(const float* g, uint32_t lds) {
+    unsigned keep;
+    asm volatile(
+        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+        "global_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+        : "=&s"(keep) : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds)) : "memory");
 }
 
 // Four one-KiB LDS-DMA pieces under one M0 value (instruction offsets move both the global source
@@ -53,7 +74,7 @@ __device__ __forceinline__ void dma1_at(int j, const void* sbase, uint32_t lds0,
     }
 }
 
-// one dword per lane (the row norms of a tile)
+// one dword per lane (the row norms or the list entries of a tile)
 __device__ __forceinline__ void dma4_norm(const float* g, uint32_t lds) {
     unsigned keep;
     asm volatile(
@@ -77,6 +98,13 @@ __device__ __forceinline__ void dma2_agent(const void* sbase, uint32_t lds0, uin
         : "memory");
 }
 
+// The counted wait of a DMA ring: at most N of this wave's DMA instructions still in flight.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+
+// s_barrier that also orders the compiler's LDS accesses (the intrinsic alone is IntrNoMem).
 __device__ __forceinline__ void barrier_lds() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");

@@ -37,6 +37,7 @@
 
 #include "../../include/imgrec_vit.h"
 #include "lds_dma.h"
+#include "wave_ops.h"
 
 namespace imgrec {
 namespace {
@@ -122,9 +123,7 @@ vit_gemm_kernel(const uint32_t* __restrict__ xw, const uint32_t* __restrict__ ww
 
     // XCD-aware bijective block -> (feature block, token split) map (knn_b16w.hip): the G
     // feature-block workgroups of a token split get consecutive ids on one XCD
-    const int nwg = gridDim.x, wg = blockIdx.x;
-    const int xcd = wg & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int wgid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (wg >> 3);
+    const int wgid = xcd_wgid();
     const int G = (nqb % 4 == 0) ? 4 : nqb;
     const int qbg = wgid / (nsplit * G), rem = wgid - qbg * (nsplit * G);
     const int split = rem / G;

@@ -19,6 +19,15 @@ __device__ __forceinline__ float key_from_ordered(uint32_t u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
+// XCD-aware, bijective map of a launch's block index to a work item id: blocks b and b+8 share an
+// XCD; consecutive remapped ids (same XCD) share a row split (or a GEMM's operand panel), so the
+// stages they stream are served from that XCD's L2 for all of them.
+__device__ __forceinline__ int xcd_wgid() {
+    const int nwg = gridDim.x, wg = blockIdx.x;
+    const int xcd = wg & 7, qq = nwg >> 3, rr = nwg & 7;
+    return (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (wg >> 3);
+}
+
 // Wave-wide minimum of a u64 with DPP row shifts (in-row prefix minimum, lanes shifting in from
 // outside the row keep the identity) and four lane reads: the result is uniform (SGPRs).  Replaces
 // a 6-step shuffle butterfly whose LDS-crossbar latency dominated the merge rounds.

@@ -223,3 +223,22 @@ def test_device_form(faiss, devices):
     ti = torch.as_tensor(_DeviceArray(pi, res.size, "<i8"), device="cuda")
     _same(ref, (tl.cpu().numpy(), td.cpu().numpy(), ti.cpu().numpy()))
     del tl, td, ti, res
+
+
+@pytest.mark.parametrize("metric", ["l2", "ip"])
+@pytest.mark.parametrize("nq", [5, 130])
+@pytest.mark.parametrize("d", [48, 80])
+def test_exact_topk_equals_range_prefix(faiss, d, nq, metric):
+    """The top-k, range and filter kernels run one tile core (csrc/knn_tile.h): one depth order,
+    one key formula.  Where the row stride is no multiple of 32 (d = 48, 80) every exact geometry
+    and the range kernel use 16-deep stages, so the search_mode="exact" top-k is the k-prefix of
+    range_search(all rows) byte for byte, D and I, padded as a search pads.  N = 3000: several tiles
+    per geometry, the last one partial; nq = 5 / 130: the 256 x 32 and the 128 x 128 geometry."""
+    from tests.test_filter_gpu import _prefix_of_range
+    rng = np.random.default_rng(1000 * d + nq)
+    xb = rng.standard_normal((3000, d)).astype(np.float32)
+    xq = rng.standard_normal((nq, d)).astype(np.float32)
+    idx = _index(faiss, d, metric)
+    idx.add(xb)
+    idx.search_mode = "exact"
+    _same(idx.search(xq, 10), _prefix_of_range(idx, xq, 10, metric))

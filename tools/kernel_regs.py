@@ -46,16 +46,19 @@ def main():
     if a.rev:
         td = tempfile.mkdtemp()
         rel = os.path.relpath(CSRC, ROOT)
-        for f in subprocess.run(["git", "ls-tree", "--name-only", a.rev, rel + "/"], cwd=ROOT,
+        # the same layout as the tree: csrc headers include ../../include/*.h
+        for f in subprocess.run(["git", "ls-tree", "--name-only", a.rev, rel + "/", "include/"], cwd=ROOT,
                                 capture_output=True, text=True, check=True).stdout.split():
-            with open(os.path.join(td, os.path.basename(f)), "w") as fh:
+            os.makedirs(os.path.dirname(os.path.join(td, f)), exist_ok=True)
+            with open(os.path.join(td, f), "w") as fh:
                 fh.write(subprocess.run(["git", "show", f"{a.rev}:{f}"], cwd=ROOT, capture_output=True,
                                         text=True, check=True).stdout)
-        src, inc = os.path.join(td, os.path.basename(a.src)), td
+        inc = os.path.join(td, rel)
+        src = os.path.join(inc, os.path.basename(a.src))
     for r in table(src, inc):
         if a.filter not in r["name"]:
             continue
-        print(f"{r.get('VGPRs', '?'):>4} v {r.get('AGPRs', '?'):>4} a  spill s {r.get('SGPRs Spill', '?'):>3}"
+        print(f"{r.get('VGPRs', '?'):>4} v {r.get('AGPRs', '?'):>4} a {r.get('TotalSGPRs', '?'):>4} s  spill s {r.get('SGPRs Spill', '?'):>3}"
               f" v {r.get('VGPRs Spill', '?'):>3}  lds {r.get('LDS Size', '?'):>6}  {r['name'][:110]}")
 
 

@@ -60,6 +60,7 @@ class IndexIVFPQ:
         self.niter, self.pq_niter, self.seed = int(niter), int(pq_niter), int(seed)
         self.max_points_per_centroid = int(max_points_per_centroid)
         self.nprobe = 1
+        self.table_bytes = 1 << 30     # most distance-table bytes of one search chunk
         self.device = torch.device("cuda", device if device >= 0 else torch.cuda.current_device())
         self.is_trained = False
         self.centroids = None          # (nlist, d) float32
@@ -201,8 +202,9 @@ class IndexIVFPQ:
             raise ValueError("add_encoded: list id out of range")
         if codes.numel() and (int(codes.min()) < 0 or int(codes.max()) >= self.ksub):
             raise ValueError("add_encoded: code out of range")
-        if ids.numel() and int(ids.max()) >= 2 ** 31:
-            raise ValueError("add_encoded: labels must be < 2^31")
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= 2 ** 31):
+            # (the register scan reads a negative label as an empty slot; the sort route keeps 32 bits)
+            raise ValueError("add_encoded: labels must be in [0, 2^31)")
         all_lists = torch.cat([self._lists, lists])
         all_codes = torch.cat([self._codes.to(torch.int64) & 0xffff, codes])
         all_ids = torch.cat([self._ids, ids])
@@ -232,7 +234,7 @@ class IndexIVFPQ:
             return D.cpu().numpy(), I.cpu().numpy()
         lib = _lib.load()
         st = torch.cuda.current_stream(self.device).cuda_stream
-        chunk = max(1, (1 << 30) // (npb * self.m * self.ksub * 4))     # <= 1 GB of tables
+        chunk = max(1, int(self.table_bytes) // (npb * self.m * self.ksub * 4))     # <= 1 GB of tables
         for q0 in range(0, nq, chunk):
             q1 = min(nq, q0 + chunk)
             qc = q[q0:q1]

@@ -36,7 +36,8 @@ int ivfpq_lut_device(const float* residuals, int64_t nr, int d, int m, int ksub,
                      const float* codebooks_t, float* lut, void* stream);
 
 /* ADC scan of each query's probed lists: distance of a row = sum_j lut[q*nprobe+p][j][code_j];
- * the k best per query over all its probes.  k <= 32. */
+ * the k best per query over all its probes.  k <= 32.  Labels in [0, 2^31): the kernel keeps a
+ * label in 32 signed bits and reads a negative one as an empty slot, so such a row is dropped. */
 int ivfpq_scan_device(const float* lut, const int64_t* probes, int64_t nq, int nprobe,
                       const int64_t* list_off, const uint16_t* codes, const int64_t* ids, int m,
                       int ksub, int k, float* D, int64_t* I, void* stream);
@@ -46,8 +47,9 @@ int ivfpq_scan_device(const float* lut, const int64_t* probes, int64_t nq, int n
  * label -1 / FLT_MAX.  probe_off (nq x nprobe int64): the first slot of (query q, probe p) in a
  * buffer of `total` entries, the rows of that probe's list in list order (0 rows for a -1 probe);
  * seg_off (nq + 1 uint32): query q's entries are [seg_off[q], seg_off[q + 1]), seg_off[nq] =
- * total < 2^32.  Labels < 2^32.  Work space (2 x total x 8 B + the sort's) is allocated and freed
- * in stream order on `stream`. */
+ * total < 2^32.  Labels in [0, 2^32) (the low 32 bits are kept); an index searched through both
+ * routes keeps to ivfpq_scan_device's [0, 2^31).  Work space (2 x total x 8 B + the sort's) is
+ * allocated and freed in stream order on `stream`. */
 int ivfpq_scan_all_device(const float* lut, const int64_t* probes, int64_t nq, int nprobe,
                           const int64_t* list_off, const uint16_t* codes, const int64_t* ids, int m,
                           int ksub, const int64_t* probe_off, const uint32_t* seg_off, int64_t total,

@@ -1,6 +1,6 @@
 // knn_hugek.hip — exact search and list merges for k > KNN_MAX_K_LARGE (any k: faiss IndexFlat
 // serves every k, padding past ntotal with label -1; the reference passes the CLI's --top-k
-// straight to index.search, /root/reference/main/search_from_image.py:27, 247).
+// straight to index.search, main/search_from_image.py:27, 247).
 //
 // The in-LDS large-k route (knn_largek.hip) selects from 32-entry lists and its radix select holds
 // at most 8192 values per query.  Past k = 1024 the answer is a large fraction of a list union
@@ -148,7 +148,10 @@ __global__ void hugek_pack_lists_kernel(const float* __restrict__ cD, const int6
     const int64_t l = e / kin, p = e - l * kin;
     const int64_t lab = cI[l * si + q * kin + p];
     const float d = cD[l * sd + q * kin + p];
-    v[q * M + e] = lab < 0 ? ~0ull : ((uint64_t)key_bits_ordered(metric == 1 ? d : -d) << 32) | (uint32_t)lab;
+    // (+ 0.0f: -0.0 becomes +0.0, so equal keys pack equal bits and the label decides, as in the
+    // float comparison of the k <= KNN_MAX_K merge)
+    const float key = (metric == 1 ? d : -d) + 0.0f;
+    v[q * M + e] = lab < 0 ? ~0ull : ((uint64_t)key_bits_ordered(key) << 32) | (uint32_t)lab;
 }
 
 int bits_for(int64_t n) {                      // bits a row index < n needs

@@ -412,7 +412,8 @@ largek_final_kernel(const uint64_t* __restrict__ run, int S, int k, const int* _
 // Merge of nlists sorted per-shard results of kin entries per query (distance-ascending for L2,
 // inner-product-descending otherwise; label -1 = empty) into the final top-k for k > KNN_MAX_K:
 // list l of query q at cD[l * sd + q * kin], cI[l * si + q * kin].  Labels must be < 2^32 (they
-// pack beside the key; ties order by label, faiss's rule).
+// pack beside the key; ties order by label, faiss's rule: include/imgrec_knn.h knn_merge_device
+// states the contract, the callers that know their label range enforce it).
 __global__ void __launch_bounds__(kLKThreads)
 largek_merge_kernel(const float* __restrict__ cD, const int64_t* __restrict__ cI, int nlists,
                     int kin, int64_t sd, int64_t si, int k, int metric, float* __restrict__ D,
@@ -429,7 +430,10 @@ largek_merge_kernel(const float* __restrict__ cD, const int64_t* __restrict__ cI
         const int l = e / kin, p = e - l * kin;
         const int64_t lab = cI[l * si + q * kin + p];
         const float d = cD[l * sd + q * kin + p];
-        v[e] = lab < 0 ? ~0ull : ((uint64_t)key_bits_ordered(metric == 1 ? d : -d) << 32) | (uint32_t)lab;
+        // (+ 0.0f: -0.0 becomes +0.0, so equal keys pack equal bits and the label decides, as in
+        // the float comparison of the k <= KNN_MAX_K merge)
+        const float key = (metric == 1 ? d : -d) + 0.0f;
+        v[e] = lab < 0 ? ~0ull : ((uint64_t)key_bits_ordered(key) << 32) | (uint32_t)lab;
     }
     __syncthreads();
     select_k(v, M, k, sel, hist, &s_prefix, &s_rem, &s_nlt, true);

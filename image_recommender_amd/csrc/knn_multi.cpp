@@ -335,6 +335,10 @@ int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, i
     knn_multi* m = M(ix);
     const int ndev = (int)m->shards.size();
     const size_t nk = (size_t)nq * k;
+    // the k > KNN_MAX_K merges pack a label into 32 bits (include/imgrec_knn.h knn_merge_device)
+    if (k > KNN_MAX_K && ix->ntotal + ix->id_offset > (int64_t(1) << 32))
+        KNN_FAIL(KNN_EINVAL, "k = %d > %d over shards: labels must stay below 2^32, ntotal + id_offset = %lld",
+                 k, KNN_MAX_K, (long long)(ix->ntotal + ix->id_offset));
     int rc;
     {
         DeviceGuard g(ix->device);

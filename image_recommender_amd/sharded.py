@@ -30,6 +30,9 @@ from . import _lib
 from .faiss_compat import METRIC_L2, Index, _METRIC_TO_KNN
 
 
+MERGE_LABEL_END = 1 << 32       # labels a k > KNN_MAX_K merge carries: [0, 2^32)
+
+
 def shard_range(ntotal: int, rank: int, world: int) -> tuple[int, int]:
     """Contiguous balanced row range of `rank` (same formula as the kernel's row splits)."""
     return ntotal * rank // world, ntotal * (rank + 1) // world
@@ -68,12 +71,26 @@ def gather_results(D, I, group=None):
     return gD, gI
 
 
-def merge_gathered_device(gD, gI, k: int, metric: int = METRIC_L2, stream: int = 0):
-    """HIP merge of gathered (world, nq, kin) device results into the final (nq, k)."""
+def check_merge_labels(label_end: int, k: int) -> None:
+    """Refuse a merge whose labels the k > KNN_MAX_K kernels would truncate: they pack a label into
+    32 bits beside its key (include/imgrec_knn.h knn_merge_device), the k <= KNN_MAX_K kernel
+    carries all 64.  label_end: one past the largest label the lists can hold."""
+    if k > _lib.KNN_MAX_K and label_end > MERGE_LABEL_END:
+        raise ValueError(f"a merge of k = {k} > {_lib.KNN_MAX_K} lists needs labels below 2^32, "
+                         f"these reach {label_end - 1}: search with k <= {_lib.KNN_MAX_K} or "
+                         "index fewer rows")
+
+
+def merge_gathered_device(gD, gI, k: int, metric: int = METRIC_L2, stream: int = 0, out=None):
+    """HIP merge of gathered (world, nq, kin) device results into the final (nq, k) (out:
+    optional contiguous (D, I) to write into).  k > KNN_MAX_K: labels in [0, 2^32)."""
     import torch
     world, nq, kin = gD.shape
-    D = torch.empty((nq, k), dtype=torch.float32, device=gD.device)
-    I = torch.empty((nq, k), dtype=torch.int64, device=gD.device)
+    if out is not None:
+        D, I = out
+    else:
+        D = torch.empty((nq, k), dtype=torch.float32, device=gD.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=gD.device)
     _lib.check(_lib.load().knn_merge_device(
         C.c_void_p(gD.data_ptr()), C.c_void_p(gI.data_ptr()), int(world), int(nq), int(kin),
         int(k), _METRIC_TO_KNN[metric], C.c_void_p(D.data_ptr()), C.c_void_p(I.data_ptr()),
@@ -118,7 +135,7 @@ def gather_packed(buf, group=None, out=None):
 def merge_packed_device(g, nq: int, kin: int, k: int, metric: int = METRIC_L2, stream: int = 0,
                         out=None):
     """HIP merge (knn_merge_packed_device) of gathered packed chunks (nchunks, nbytes) -> (nq, k)
-    (out: optional contiguous (D, I) views to write into)."""
+    (out: optional contiguous (D, I) views to write into).  k > KNN_MAX_K: labels in [0, 2^32)."""
     import torch
     world = g.shape[0]
     if out is not None:
@@ -170,11 +187,13 @@ class ShardedIndex:
 
     def search(self, q, k: int, events=None):
         """q: (nq, d) float32 device tensor, identical on every rank -> (D, I) on every rank.
+        ValueError for k > KNN_MAX_K over more than 2^32 global rows (check_merge_labels).
 
         events: optional 4 torch.cuda.Event recorded on the search stream before the local search,
         after it, after the all-gather and after the merge (bench.py's per-rank phase times; each
         record costs a few us of GPU time, so timed regions leave it None)."""
         import torch
+        check_merge_labels(self.ntotal_global, k)
         nq = q.shape[0]
         cs = torch.cuda.current_stream(q.device)
         st = cs.cuda_stream

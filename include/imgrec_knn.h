@@ -260,14 +260,23 @@ int knn_search_filtered_device(knn_index_t* index, const float* q_dev, int64_t n
 
 /* Merge nlists candidate lists per query into the top k.  cand_D/cand_I are laid out
  * [nlists][nq][kin] (the layout of an all-gather of per-shard [nq][kin] results); entries with
- * label -1 are ignored.  Output nq*k, same ordering/padding rules as knn_search. */
+ * label -1 are ignored.  Output nq*k, same ordering/padding rules as knn_search: the k best by
+ * (key, label), keys compared as floats (-0.0 ties +0.0, the smaller label first), then label -1
+ * and +-FLT_MAX.
+ * Labels: k <= KNN_MAX_K carries any non-negative int64.  For k > KNN_MAX_K every label must lie
+ * in [0, 2^32): those kernels pack a label into 32 bits beside its key, and a larger one comes
+ * back without its upper bits.  The device cannot refuse without a host read, so the callers that
+ * know their label range do: a multi-device index returns KNN_EINVAL for a k > KNN_MAX_K search
+ * when ntotal + id_offset > 2^32, ShardedIndex.search raises when ntotal_global > 2^32. */
 int knn_merge_device(const float* cand_D, const int64_t* cand_I, int nlists, int64_t nq, int kin,
                      int k, int metric, float* D_dev, int64_t* I_dev, void* stream);
 
 /* Packed per-shard results: one chunk of knn_packed_bytes(nq, k) bytes per shard holding the nq*k
  * float keys (padded to an even count), then the nq*k int64 labels (8-byte aligned).  A shard
  * searches straight into its chunk (D = chunk, I = chunk + 4 * (nq*k rounded up to even)); one
- * all-gather of the chunks gives knn_merge_packed_device its [nlists] chunks. */
+ * all-gather of the chunks gives knn_merge_packed_device its [nlists] chunks.  The padding float
+ * is never read.  Order, padding and the label contract are knn_merge_device's: any non-negative
+ * int64 label for k <= KNN_MAX_K, labels in [0, 2^32) for k > KNN_MAX_K. */
 int64_t knn_packed_bytes(int64_t nq, int k);
 int knn_merge_packed_device(const void* packed, int nlists, int64_t nq, int kin, int k, int metric,
                             float* D_dev, int64_t* I_dev, void* stream);

@@ -16,6 +16,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from tests.datagen import mixture
+from tests.merge_check import merge_reference as _merge_oracle
 
 
 def _free_port():
@@ -24,23 +25,6 @@ def _free_port():
     p = s.getsockname()[1]
     s.close()
     return p
-
-
-def _merge_oracle(gD, gI, k, metric):
-    """Reference semantics of knn_merge_device: best k of the gathered lists by (key, label)."""
-    world, nq, kin = gD.shape
-    D = np.empty((nq, k), np.float64)
-    I = np.empty((nq, k), np.int64)
-    for q in range(nq):
-        d = gD[:, q, :].reshape(-1)
-        i = gI[:, q, :].reshape(-1)
-        ok = i >= 0
-        key = d[ok] if metric == "l2" else -d[ok]
-        order = np.lexsort((i[ok], key))[:k]
-        n = len(order)
-        D[q, :n], I[q, :n] = d[ok][order], i[ok][order]
-        D[q, n:], I[q, n:] = (np.finfo(np.float32).max if metric == "l2" else -np.finfo(np.float32).max), -1
-    return D, I
 
 
 def _worker(rank, world, port, n, d, nq, k, metric, out, packed=False):

@@ -1,7 +1,9 @@
 // knn_capi.cpp — the C ABI of include/imgrec_knn.h: index lifetime, the HBM corpus buffer, adds,
 // searches, merges, timing and stats.  The search paths live in knn_search.cpp, the launch
 // geometry in knn_plan.cpp, the file layout in knn_io.cpp, the multi-device index in
-// knn_multi.cpp.
+// knn_multi.cpp.  The index's memory is owned by its DevBuf / PinBuf members (knn_index.h):
+// free_single only quiesces the device and deletes the index; the corpus's per-row arrays are
+// listed once, in corpus_columns.
 //
 // Reference call sites each entry point replaces are listed in include/imgrec_knn.h.
 //
@@ -104,76 +106,65 @@ int fence_end_synced(knn_index* ix) {
     return KNN_OK;
 }
 
-// Grow the corpus buffers (fp32 rows, norms, split / bf16 copies) to hold `need` rows; the
-// copies of the existing rows run on `st` (ordered after the adds that wrote them), which is
-// synchronised before the old buffers are released.
+// The corpus column table: every per-row array of the index with its row stride in bytes.
+// reserve_rows, remove_rows_locked, add_device_locked, ensure_split and ensure_i8 all go through
+// it, so a new column is added here (and its ingest launch to add_device_locked) and nowhere else.
+int corpus_columns(knn_index* ix, Column<DeviceSpace>* cols, bool all) {
+    int n = 0;
+    cols[n++] = {&ix->xb, (size_t)ix->dp * sizeof(float)};
+    cols[n++] = {&ix->xn, sizeof(float)};
+    // the split copy exists only once a split-mode search has materialised it (ensure_split)
+    if (all || ix->xs) cols[n++] = {&ix->xs, (size_t)ix->dp * sizeof(uint32_t)};
+    if (all || ix->b16_ok) cols[n++] = {&ix->xh, (size_t)ix->dpb * sizeof(uint16_t)};
+    if (all || ix->b16_ok) cols[n++] = {&ix->xr, sizeof(float)};
+    // the int8 copy exists only once a small-batch search has materialised it (ensure_i8)
+    if (all || ix->x8) cols[n++] = {&ix->x8, (size_t)i8_row_bytes(ix->nblk8)};
+    if (all || ix->x8) cols[n++] = {&ix->x8s, (size_t)ix->nblk8 * sizeof(float)};
+    if (all || ix->x8) cols[n++] = {&ix->x8r, sizeof(float)};
+    return n;
+}
+
+// Grow the corpus buffers (every live column) to hold `need` rows; the copies of the existing rows
+// run on `st` (ordered after the adds that wrote them), which is synchronised before the columns
+// take their new blocks and the old ones are released (regrow_columns: all columns or none).
 int reserve_rows(knn_index* ix, int64_t need, hipStream_t st) {
     if (need <= ix->cap) return KNN_OK;
     const int64_t ncap = round_up(std::max(need, ix->cap + ix->cap / 2), kTileRowsMax);
-    float* nxb = nullptr;
-    float* nxn = nullptr;
-    uint32_t* nxs = nullptr;
-    uint16_t* nxh = nullptr;
-    float* nxr = nullptr;
-    int8_t* nx8 = nullptr;
-    float* nx8s = nullptr;
-    float* nx8r = nullptr;
-    auto release = [&]() {
-        for (void* p : {(void*)nxb, (void*)nxn, (void*)nxs, (void*)nxh, (void*)nxr, (void*)nx8,
-                        (void*)nx8s, (void*)nx8r})
-            if (p) (void)hipFree(p);
-    };
-    hipError_t e = hipMalloc((void**)&nxb, (size_t)ncap * ix->dp * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&nxn, (size_t)ncap * sizeof(float));
-    // the split copy exists only once a split-mode search has materialised it (ensure_split)
-    if (e == hipSuccess && ix->xs) e = hipMalloc((void**)&nxs, (size_t)ncap * ix->dp * sizeof(uint32_t));
-    if (e == hipSuccess && ix->b16_ok) e = hipMalloc((void**)&nxh, (size_t)ncap * ix->dpb * sizeof(uint16_t));
-    if (e == hipSuccess && ix->b16_ok) e = hipMalloc((void**)&nxr, (size_t)ncap * sizeof(float));
-    // the int8 copy exists only once a small-batch search has materialised it (ensure_i8)
-    const size_t row8 = (size_t)i8_row_bytes(ix->nblk8);
-    if (e == hipSuccess && ix->x8) e = hipMalloc((void**)&nx8, (size_t)ncap * row8);
-    if (e == hipSuccess && ix->x8) e = hipMalloc((void**)&nx8s, (size_t)ncap * ix->nblk8 * sizeof(float));
-    if (e == hipSuccess && ix->x8) e = hipMalloc((void**)&nx8r, (size_t)ncap * sizeof(float));
-    if (e != hipSuccess) {
-        release();
+    Column<DeviceSpace> live[kCorpusColumns];
+    const int n = corpus_columns(ix, live);
+    const size_t old = (size_t)ix->ntotal;
+    hipError_t e = hipSuccess;
+    const int rc = regrow_columns(
+        live, n, (size_t)ncap,
+        [&](int i, void* dst, const void* src) {
+            const size_t row = live[i].stride;
+            if (old && src) e = hipMemcpyAsync(dst, src, old * row, hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = hipMemsetAsync((char*)dst + old * row, 0, ((size_t)ncap - old) * row, st);
+            return e == hipSuccess ? KNN_OK : KNN_EHIP;
+        },
+        [&]() {
+            const hipError_t es = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = es;
+            return e == hipSuccess ? KNN_OK : KNN_EHIP;
+        });
+    if (rc != KNN_OK && e == hipSuccess) {   // no fill or wait failed: an allocation did
         (void)hipGetLastError();
         KNN_FAIL(KNN_ENOMEM, "hipMalloc of the %lld-row corpus buffers failed", (long long)ncap);
     }
-    const size_t old = (size_t)ix->ntotal;
-    auto copy_tail = [&](void* dst, const void* src, size_t row_bytes, size_t rows_cap) -> hipError_t {
-        hipError_t r = hipSuccess;
-        if (old && src) r = hipMemcpyAsync(dst, src, old * row_bytes, hipMemcpyDeviceToDevice, st);
-        if (r == hipSuccess)
-            r = hipMemsetAsync((char*)dst + old * row_bytes, 0, (rows_cap - old) * row_bytes, st);
-        return r;
-    };
-    e = copy_tail(nxb, ix->xb, (size_t)ix->dp * sizeof(float), (size_t)ncap);
-    if (e == hipSuccess) e = copy_tail(nxn, ix->xn, sizeof(float), (size_t)ncap);
-    if (e == hipSuccess && nxs) e = copy_tail(nxs, ix->xs, (size_t)ix->dp * sizeof(uint32_t), (size_t)ncap);
-    if (e == hipSuccess && nxh) e = copy_tail(nxh, ix->xh, (size_t)ix->dpb * sizeof(uint16_t), (size_t)ncap);
-    if (e == hipSuccess && nxr) e = copy_tail(nxr, ix->xr, sizeof(float), (size_t)ncap);
-    if (e == hipSuccess && nx8) e = copy_tail(nx8, ix->x8, row8, (size_t)ncap);
-    if (e == hipSuccess && nx8s) e = copy_tail(nx8s, ix->x8s, (size_t)ix->nblk8 * sizeof(float), (size_t)ncap);
-    if (e == hipSuccess && nx8r) e = copy_tail(nx8r, ix->x8r, sizeof(float), (size_t)ncap);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        release();
-        KNN_FAIL(KNN_EHIP, "corpus regrowth failed: %s", hipGetErrorString(e));
-    }
-    for (void* p : {(void*)ix->xb, (void*)ix->xn, (void*)ix->xs, (void*)ix->xh, (void*)ix->xr,
-                    (void*)ix->x8, (void*)ix->x8s, (void*)ix->x8r})
-        if (p) (void)hipFree(p);
-    ix->x8 = nx8;
-    ix->x8s = nx8s;
-    ix->x8r = nx8r;
-    ix->xb = nxb;
-    ix->xn = nxn;
-    ix->xs = nxs;
-    ix->xh = nxh;
-    ix->xr = nxr;
+    if (rc != KNN_OK) KNN_FAIL(KNN_EHIP, "corpus regrowth failed: %s", hipGetErrorString(e));
     ix->cap = ncap;
     return KNN_OK;
+}
+
+// A lazily built copy's columns (table entries c0 .. c0 + n - 1) at the index's capacity, all or
+// none; the caller fills them from the fp32 rows.
+static int materialise_columns(knn_index* ix, int c0, int n) {
+    Column<DeviceSpace> all[kCorpusColumns];
+    corpus_columns(ix, all, true);
+    const int rc = regrow_columns(all + c0, n, (size_t)std::max<int64_t>(ix->cap, 1),
+                                  [](int, void*, const void*) { return KNN_OK; }, []() { return KNN_OK; });
+    if (rc != KNN_OK) (void)hipGetLastError();
+    return rc;
 }
 
 int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st) {
@@ -181,18 +172,19 @@ int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st) 
         KNN_FAIL(KNN_EINVAL, "a single index shard holds at most 2^31-1 rows");
     int rc = reserve_rows(ix, ix->ntotal + n, st);
     if (rc != KNN_OK) return rc;
-    KNN_HIP(launch_rows_ingest(x, n, ix->d, ix->dp, n, ix->metric == KNN_METRIC_COSINE ? 1 : 0,
-                               ix->xb + (size_t)ix->ntotal * ix->dp, ix->xn + ix->ntotal, st));
-    if (ix->xs)
-        KNN_HIP(launch_split_rows(ix->xb + (size_t)ix->ntotal * ix->dp, n, ix->dp, kSplitBK,
-                                  ix->xs + (size_t)ix->ntotal * ix->dp, st));
+    // the new rows' place in every column (the ingest launches stay explicit: different kernels)
+    Column<DeviceSpace> c[kCorpusColumns];
+    corpus_columns(ix, c, true);
+    auto at = [&](int col) { return (char*)c[col].buf->data() + (size_t)ix->ntotal * c[col].stride; };
+    float* const xb = (float*)at(kColXb);
+    KNN_HIP(launch_rows_ingest(x, n, ix->d, ix->dp, n, ix->metric == KNN_METRIC_COSINE ? 1 : 0, xb,
+                               (float*)at(kColXn), st));
+    if (ix->xs) KNN_HIP(launch_split_rows(xb, n, ix->dp, kSplitBK, (uint32_t*)at(kColXs), st));
     if (ix->b16_ok)
-        KNN_HIP(launch_bf16_rows(ix->xb + (size_t)ix->ntotal * ix->dp, n, ix->dp, ix->dpb,
-                                 ix->xh + (size_t)ix->ntotal * ix->dpb, ix->xr + ix->ntotal, st));
+        KNN_HIP(launch_bf16_rows(xb, n, ix->dp, ix->dpb, (uint16_t*)at(kColXh), (float*)at(kColXr), st));
     if (ix->x8)
-        KNN_HIP(launch_i8_rows(ix->xb + (size_t)ix->ntotal * ix->dp, n, ix->dp, ix->nblk8,
-                               ix->x8 + (size_t)ix->ntotal * i8_row_bytes(ix->nblk8),
-                               ix->x8s + (size_t)ix->ntotal * ix->nblk8, ix->x8r + ix->ntotal, st));
+        KNN_HIP(launch_i8_rows(xb, n, ix->dp, ix->nblk8, (int8_t*)at(kColX8), (float*)at(kColX8s),
+                               (float*)at(kColX8r), st));
     ix->ntotal += n;
     ix->xn_max_stale = true;
     return KNN_OK;
@@ -205,12 +197,8 @@ int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st) 
 int ensure_split(knn_index* ix, hipStream_t st) {
     if (ix->xs) return KNN_OK;
     if (!ix->split_ok) KNN_FAIL(KNN_EINVAL, "split search needs d >= 256; d = %d", ix->d);
-    uint32_t* xs = nullptr;
-    if (hipMalloc((void**)&xs, (size_t)std::max<int64_t>(ix->cap, 1) * ix->dp * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
+    if (materialise_columns(ix, kColXs, 1) != KNN_OK)
         KNN_FAIL(KNN_ENOMEM, "hipMalloc of the %lld-row split copy failed", (long long)ix->cap);
-    }
-    ix->xs = xs;
     if (ix->ntotal > 0)
         KNN_HIP(launch_split_rows(ix->xb, ix->ntotal, ix->dp, kSplitBK, ix->xs, st));
     return KNN_OK;
@@ -222,22 +210,8 @@ int ensure_split(knn_index* ix, hipStream_t st) {
 int ensure_i8(knn_index* ix, hipStream_t st) {
     if (ix->x8) return KNN_OK;
     if (ix->nblk8 <= 0) KNN_FAIL(KNN_EINVAL, "int8 search needs 64 <= d <= 4096; d = %d", ix->d);
-    const size_t cap = (size_t)std::max<int64_t>(ix->cap, 1);
-    int8_t* x8 = nullptr;
-    float* x8s = nullptr;
-    float* x8r = nullptr;
-    hipError_t e = hipMalloc((void**)&x8, cap * (size_t)i8_row_bytes(ix->nblk8));
-    if (e == hipSuccess) e = hipMalloc((void**)&x8s, cap * ix->nblk8 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&x8r, cap * sizeof(float));
-    if (e != hipSuccess) {
-        for (void* p : {(void*)x8, (void*)x8s, (void*)x8r})
-            if (p) (void)hipFree(p);
-        (void)hipGetLastError();
+    if (materialise_columns(ix, kColX8, 3) != KNN_OK)
         KNN_FAIL(KNN_ENOMEM, "hipMalloc of the %lld-row int8 copy failed", (long long)ix->cap);
-    }
-    ix->x8 = x8;
-    ix->x8s = x8s;
-    ix->x8r = x8r;
     ix->xn_max_stale = true;             // refresh_maxima computes the int8 residual maximum
     if (ix->ntotal > 0)
         KNN_HIP(launch_i8_rows(ix->xb, ix->ntotal, ix->dp, ix->nblk8, ix->x8, ix->x8s, ix->x8r, st));
@@ -323,32 +297,10 @@ int create_single(int d, int metric, int device, knn_index** out) {
 void free_single(knn_index* ix) {
     DeviceGuard g(ix->device);
     (void)hipDeviceSynchronize();       // searches on other streams may still use the buffers
-    for (void* p : {(void*)ix->x8, (void*)ix->x8s, (void*)ix->x8r, (void*)ix->x8r_max,
-                    (void*)ix->q8, (void*)ix->q8s, (void*)ix->q8r})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)ix->pq, (void*)ix->pd, (void*)ix->pi})
-        if (p) (void)hipHostFree(p);
-    for (void* p : {(void*)ix->xh, (void*)ix->xr, (void*)ix->xr_max, (void*)ix->qb16,
-                    (void*)ix->q_resid, (void*)ix->floor, (void*)ix->mws_d, (void*)ix->mws_i,
-                    (void*)ix->mws_f, (void*)ix->stat, (void*)ix->fb_cd, (void*)ix->fb_ci,
-                    (void*)ix->sbound,
-                    (void*)ix->tail_ctl, (void*)ix->chance, (void*)ix->sc_key, (void*)ix->sc_lab,
-                    (void*)ix->sc_meta, (void*)ix->sc_done, (void*)ix->heads, (void*)ix->i8_dyn})
-        if (p) (void)hipFree(p);
-    for (void* p : {(void*)ix->xb, (void*)ix->xn, (void*)ix->xs, (void*)ix->xn_max,
-                    (void*)ix->qpad, (void*)ix->qnorm, (void*)ix->cand_d, (void*)ix->cand_i,
-                    (void*)ix->qsplit, (void*)ix->cand2_d, (void*)ix->cand2_i, (void*)ix->fail,
-                    (void*)ix->fb_q, (void*)ix->fb_qn, (void*)ix->hq, (void*)ix->hd, (void*)ix->hi})
-        if (p) (void)hipFree(p);
-    largek_free(ix);
-    hugek_free(ix);
-    range_free(ix);
-    filter_free(ix);
-    remove_free(ix);
     for (hipEvent_t e : ix->ev) (void)hipEventDestroy(e);
     if (ix->fence) (void)hipEventDestroy(ix->fence);
     (void)hipStreamDestroy(ix->stream);
-    delete ix;
+    delete ix;                          // (every buffer, while the guard holds)
 }
 
 // The host form's inputs onto the index's device, on its own stream: the queries into hq, room for
@@ -359,10 +311,10 @@ int filtered_stage_host(knn_index* ix, const float* q, int64_t nq, int k, const 
     int rc;
     *nbits = std::min(*nbits, ix->ntotal);
     const size_t nbytes = (size_t)((*nbits + 7) / 8);
-    if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)nq * ix->d)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hd, &ix->hd_cap, (size_t)nq * k)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hi, &ix->hi_cap, (size_t)nq * k)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->ft_bits, &ix->ft_bits_cap, std::max<size_t>(nbytes, 1))) != KNN_OK) return rc;
+    if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
+    if ((rc = ix->hd.reserve((size_t)nq * k)) != KNN_OK) return rc;
+    if ((rc = ix->hi.reserve((size_t)nq * k)) != KNN_OK) return rc;
+    if ((rc = ix->ft_bits.reserve(std::max<size_t>(nbytes, 1))) != KNN_OK) return rc;
     KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, ix->stream));
     if (nbytes) KNN_HIP(hipMemcpyAsync(ix->ft_bits, bitmap, nbytes, hipMemcpyHostToDevice, ix->stream));
     return KNN_OK;
@@ -465,7 +417,7 @@ int knn_add(knn_index_t* ix, const float* x, int64_t n) {
     const int64_t chunk = std::max<int64_t>(1, (int64_t)(64 << 20) / ((int64_t)ix->d * 4));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t cn = std::min(chunk, n - r0);
-        if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)cn * ix->d)) != KNN_OK) return rc;
+        if ((rc = ix->hq.reserve((size_t)cn * ix->d)) != KNN_OK) return rc;
         KNN_HIP(hipMemcpyAsync(ix->hq, x + r0 * ix->d, (size_t)cn * ix->d * sizeof(float),
                                hipMemcpyHostToDevice, ix->stream));
         if ((rc = add_device_locked(ix, ix->hq, cn, ix->stream)) != KNN_OK) return rc;
@@ -501,7 +453,7 @@ int knn_remove_ids(knn_index_t* ix, const uint8_t* bitmap, int64_t nbits, int64_
     nbits = std::min(nbits, ix->ntotal);             // bits at or past ntotal are ignored
     if (nbits > 0) {
         const size_t nbytes = (size_t)((nbits + 7) / 8);
-        if ((rc = grow(&ix->ft_bits, &ix->ft_bits_cap, nbytes)) != KNN_OK) return rc;
+        if ((rc = ix->ft_bits.reserve(nbytes)) != KNN_OK) return rc;
         KNN_HIP(hipMemcpyAsync(ix->ft_bits, bitmap, nbytes, hipMemcpyHostToDevice, ix->stream));
         if ((rc = remove_rows_locked(ix, ix->ft_bits, nbits, nullptr, nullptr, ix->stream, &n)) != KNN_OK)
             return rc;
@@ -545,17 +497,6 @@ int knn_search_device(knn_index_t* ix, const float* q, int64_t nq, int k, float*
     return fence_end(ix, st);
 }
 
-// Page-locked host buffer that only grows (the host-pointer search's staging for small batches).
-static int grow_pinned(void** p, size_t* cap, size_t need_bytes) {
-    if (*cap >= need_bytes) return KNN_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    KNN_HIP(hipHostMalloc(p, need_bytes, hipHostMallocDefault));
-    *cap = need_bytes;
-    return KNN_OK;
-}
-
 // Batches whose query rows fit this many bytes go through page-locked staging: a pageable copy
 // is a driver-staged, host-synchronous transfer on each side of a one-query search (round 1
 // measured 47 us of PCIe-side overhead per one-query search), while a memcpy of a few KB into a
@@ -572,15 +513,15 @@ int knn_search(knn_index_t* ix, const float* q, int64_t nq, int k, float* D, int
     DeviceGuard g(ix->device);
     int rc;
     if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)nq * ix->d)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hd, &ix->hd_cap, (size_t)nq * k)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hi, &ix->hi_cap, (size_t)nq * k)) != KNN_OK) return rc;
+    if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
+    if ((rc = ix->hd.reserve((size_t)nq * k)) != KNN_OK) return rc;
+    if ((rc = ix->hi.reserve((size_t)nq * k)) != KNN_OK) return rc;
     const size_t qbytes = (size_t)nq * ix->d * sizeof(float);
     const bool pinned = qbytes <= kPinnedSearchBytes;
     if (pinned) {
-        if ((rc = grow_pinned((void**)&ix->pq, &ix->pq_cap, qbytes)) != KNN_OK) return rc;
-        if ((rc = grow_pinned((void**)&ix->pd, &ix->pd_cap, (size_t)nq * k * sizeof(float))) != KNN_OK) return rc;
-        if ((rc = grow_pinned((void**)&ix->pi, &ix->pi_cap, (size_t)nq * k * sizeof(int64_t))) != KNN_OK) return rc;
+        if ((rc = ix->pq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
+        if ((rc = ix->pd.reserve((size_t)nq * k)) != KNN_OK) return rc;
+        if ((rc = ix->pi.reserve((size_t)nq * k)) != KNN_OK) return rc;
         // (the previous host-pointer search synchronised before returning: the buffers are free)
         std::memcpy(ix->pq, q, qbytes);
     }
@@ -631,7 +572,7 @@ int knn_range_search(knn_index_t* ix, const float* q, int64_t nq, float radius,
     DeviceGuard g(ix->device);
     if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
     if (nq > 0) {
-        if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)nq * ix->d)) != KNN_OK) return rc;
+        if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
         KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice,
                                ix->stream));
     }

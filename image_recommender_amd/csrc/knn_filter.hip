@@ -390,9 +390,9 @@ int compact(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lm
             hipStream_t st) {
     int rc;
     const int nblk = (int)((ix->ntotal + kCompRows - 1) / kCompRows);
-    if ((rc = grow(&ix->ft_list, &ix->ft_list_cap, (size_t)round_up(ix->ntotal, 256) + 256)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->ft_blk, &ix->ft_blk_cap, (size_t)nblk)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->ft_m, &ix->ft_m_cap, (size_t)1)) != KNN_OK) return rc;
+    if ((rc = ix->ft_list.reserve((size_t)round_up(ix->ntotal, 256) + 256)) != KNN_OK) return rc;
+    if ((rc = ix->ft_blk.reserve((size_t)nblk)) != KNN_OK) return rc;
+    if ((rc = ix->ft_m.reserve((size_t)1)) != KNN_OK) return rc;
     hipLaunchKernelGGL(filter_count_kernel, dim3((unsigned)nblk), dim3(kCompThreads), 0, st, bits, nbits,
                        lmap, ix->ntotal, invert ? 1 : 0, ix->ft_blk);
     KNN_HIP(hipGetLastError());
@@ -421,10 +421,10 @@ int filtered_lists(knn_index* ix, const float* q, int64_t nq, int k, float* D, i
     for (int64_t c0 = 0; c0 < nq; c0 += kQueryChunk) {
         const int64_t cn = std::min(kQueryChunk, nq - c0);
         const FilterPlan p = make_filter_plan(ix->ntotal, cn, k, ix->dp, ix->cus);
-        if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->qnorm, &ix->qnorm_cap, (size_t)p.nq_pad)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)cn * p.ncand)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)cn * p.ncand)) != KNN_OK) return rc;
+        if ((rc = ix->qpad.reserve((size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
+        if ((rc = ix->qnorm.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
+        if ((rc = ix->cand_d.reserve((size_t)cn * p.ncand)) != KNN_OK) return rc;
+        if ((rc = ix->cand_i.reserve((size_t)cn * p.ncand)) != KNN_OK) return rc;
         KNN_HIP(launch_rows_ingest(q + c0 * ix->d, cn, ix->d, ix->dp, p.nq_pad, normalize, ix->qpad,
                                    ix->qnorm, st));
         FilterArgs a = base_args(ix, p, cn);
@@ -444,7 +444,7 @@ int filtered_sorted(knn_index* ix, const float* q, int64_t nq, int k, float* D, 
     const int normalize = ix->metric == KNN_METRIC_COSINE;
     const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
     int rc;
-    if (!ix->ft_m_h) KNN_HIP(hipHostMalloc((void**)&ix->ft_m_h, sizeof(uint32_t), hipHostMallocDefault));
+    if ((rc = ix->ft_m_h.reserve(1)) != KNN_OK) return rc;
     KNN_HIP(hipMemcpyAsync(ix->ft_m_h, ix->ft_m, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     KNN_HIP(hipStreamSynchronize(st));
     const int64_t m = (int64_t)*ix->ft_m_h;
@@ -455,14 +455,14 @@ int filtered_sorted(knn_index* ix, const float* q, int64_t nq, int k, float* D, 
     const int64_t m_pad = round_up(m, 256);
     const int64_t per = std::max<int64_t>(1, std::min<int64_t>({nq, kFilterSortEntries / m_pad, kFilterSortMaxQ,
                                                                 kQueryChunk}));
-    if ((rc = grow(&ix->hk_a, &ix->hk_a_cap, (size_t)(per * m_pad))) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hk_b, &ix->hk_b_cap, (size_t)(per * m_pad))) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hk_off, &ix->hk_off_cap, (size_t)per + 1)) != KNN_OK) return rc;
+    if ((rc = ix->hk_a.reserve((size_t)(per * m_pad))) != KNN_OK) return rc;
+    if ((rc = ix->hk_b.reserve((size_t)(per * m_pad))) != KNN_OK) return rc;
+    if ((rc = ix->hk_off.reserve((size_t)per + 1)) != KNN_OK) return rc;
     for (int64_t c0 = 0; c0 < nq; c0 += per) {
         const int64_t cn = std::min(per, nq - c0);
         const FilterPlan p = make_filter_plan(ix->ntotal, cn, k, ix->dp, ix->cus);
-        if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->qnorm, &ix->qnorm_cap, (size_t)p.nq_pad)) != KNN_OK) return rc;
+        if ((rc = ix->qpad.reserve((size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
+        if ((rc = ix->qnorm.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
         KNN_HIP(launch_rows_ingest(q + c0 * ix->d, cn, ix->d, ix->dp, p.nq_pad, normalize, ix->qpad,
                                    ix->qnorm, st));
         KNN_HIP(hipMemsetAsync(ix->hk_a, 0xff, (size_t)(cn * m_pad) * sizeof(uint64_t), st));
@@ -473,8 +473,7 @@ int filtered_sorted(knn_index* ix, const float* q, int64_t nq, int k, float* D, 
         KNN_HIP(launch_filter_tile(p, a, st));
         if (e1) KNN_HIP(hipEventRecord(e1, st));
         // ~0 = empty (past m, or a NaN key): sorts last, written as a padding entry
-        KNN_HIP(sort_equal_segments(ix->hk_a, ix->hk_b, (int)cn, m_pad, 64u, ix->hk_off, &ix->hk_tmp,
-                                    &ix->hk_tmp_cap, false, st));
+        KNN_HIP(sort_equal_segments(ix->hk_a, ix->hk_b, (int)cn, m_pad, 64u, ix->hk_off, ix->hk_tmp, st));
         KNN_HIP(launch_sorted_write(ix->hk_b, m_pad, (int)cn, k, kmetric, 32, ix->id_offset, true, D + c0 * k,
                                     I + c0 * k, st));
     }
@@ -504,15 +503,6 @@ int filtered_search_locked(knn_index* ix, const float* q, int64_t nq, int k, con
 int compact_rows(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lmap, bool invert,
                  hipStream_t st) {
     return compact(ix, bits, nbits, lmap, invert, st);
-}
-
-void filter_free(knn_index* ix) {
-    for (void* p : {(void*)ix->ft_list, (void*)ix->ft_blk, (void*)ix->ft_m, (void*)ix->ft_bits})
-        if (p) (void)hipFree(p);
-    if (ix->ft_m_h) (void)hipHostFree(ix->ft_m_h);
-    ix->ft_list = ix->ft_blk = ix->ft_m = ix->ft_m_h = nullptr;
-    ix->ft_bits = nullptr;
-    ix->ft_list_cap = ix->ft_blk_cap = ix->ft_m_cap = ix->ft_bits_cap = 0;
 }
 
 }  // namespace imgrec

@@ -160,16 +160,13 @@ int bits_for(int64_t n) {                      // bits a row index < n needs
     return b;
 }
 
-}  // namespace
-
-hipError_t sort_equal_segments(uint64_t* in, uint64_t* out, int nseg, int64_t seg, unsigned end_bit,
-                               unsigned* off, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st) {
+hipError_t launch_offsets(unsigned* off, int nseg, int64_t seg, hipStream_t st) {
     hipLaunchKernelGGL(hugek_offsets_kernel, dim3((unsigned)((nseg + 256) / 256)), dim3(256), 0, st, off,
                        nseg, seg);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return sort_u64_segments(in, out, (int64_t)nseg * seg, nseg, off, end_bit, tmp, tmp_cap, async_tmp, st);
+    return hipGetLastError();
 }
+
+}  // namespace
 
 hipError_t launch_sorted_write(const uint64_t* sorted, int64_t seg, int nq, int k, int metric, int rb,
                                int64_t id_offset, bool label_is_row, float* D, int64_t* I, hipStream_t st) {
@@ -178,23 +175,50 @@ hipError_t launch_sorted_write(const uint64_t* sorted, int64_t seg, int nq, int 
     return hipGetLastError();
 }
 
+// an index's own temporary storage: grows (by hipMalloc) to exactly what the sort asks for
+hipError_t sort_u64_segments(uint64_t* in, uint64_t* out, int64_t total, int nseg, const unsigned* off,
+                             unsigned end_bit, DevBuf<char>& tmp, hipStream_t st) {
+    size_t need = 0;
+    const hipError_t e = rocprim::segmented_radix_sort_keys(nullptr, need, in, out, (unsigned)total,
+                                                            (unsigned)nseg, off, off + 1, 0u, end_bit, st);
+    if (e != hipSuccess) return e;
+    if (need > tmp.cap()) {
+        tmp.reset();
+        const int rc = tmp.reserve(need);
+        if (rc != KNN_OK) return rc == KNN_ENOMEM ? hipErrorOutOfMemory : hipErrorUnknown;
+    }
+    size_t have = tmp.cap();
+    return rocprim::segmented_radix_sort_keys(tmp.get(), have, in, out, (unsigned)total, (unsigned)nseg,
+                                              off, off + 1, 0u, end_bit, st);
+}
+
+// stream-ordered scratch (a merge's, IVF-PQ's): grows by hipMallocAsync on `st`, and the caller
+// frees it with hipFreeAsync.  async_tmp must be true (an index's own storage is a DevBuf).
 hipError_t sort_u64_segments(uint64_t* in, uint64_t* out, int64_t total, int nseg, const unsigned* off,
                              unsigned end_bit, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st) {
+    if (!async_tmp) return hipErrorInvalidValue;
     hipError_t e;
     size_t need = 0;
     e = rocprim::segmented_radix_sort_keys(nullptr, need, in, out, (unsigned)total, (unsigned)nseg,
                                            off, off + 1, 0u, end_bit, st);
     if (e != hipSuccess) return e;
     if (need > *tmp_cap) {
-        if (*tmp) (void)(async_tmp ? hipFreeAsync(*tmp, st) : hipFree(*tmp));
+        if (*tmp) (void)hipFreeAsync(*tmp, st);
         *tmp = nullptr;
         *tmp_cap = 0;
-        if ((e = async_tmp ? hipMallocAsync(tmp, need, st) : hipMalloc(tmp, need)) != hipSuccess) return e;
+        if ((e = hipMallocAsync(tmp, need, st)) != hipSuccess) return e;
         *tmp_cap = need;
     }
     size_t have = *tmp_cap;
     return rocprim::segmented_radix_sort_keys(*tmp, have, in, out, (unsigned)total, (unsigned)nseg,
                                               off, off + 1, 0u, end_bit, st);
+}
+
+hipError_t sort_equal_segments(uint64_t* in, uint64_t* out, int nseg, int64_t seg, unsigned end_bit,
+                               unsigned* off, DevBuf<char>& tmp, hipStream_t st) {
+    const hipError_t e = launch_offsets(off, nseg, seg, st);
+    if (e != hipSuccess) return e;
+    return sort_u64_segments(in, out, (int64_t)nseg * seg, nseg, off, end_bit, tmp, st);
 }
 
 int hugek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
@@ -210,11 +234,11 @@ int hugek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int
     const int64_t per = std::max<int64_t>(1, std::min<int64_t>({nq, kHKEntries / N, kHKMaxQ}));   // queries per chunk
     const int64_t per_pad = round_up(per, kHKT);
     int rc;
-    if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)per_pad * ix->dp)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->qnorm, &ix->qnorm_cap, (size_t)per_pad)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hk_a, &ix->hk_a_cap, (size_t)(per * N))) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hk_b, &ix->hk_b_cap, (size_t)(per * N))) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hk_off, &ix->hk_off_cap, (size_t)per + 1)) != KNN_OK) return rc;
+    if ((rc = ix->qpad.reserve((size_t)per_pad * ix->dp)) != KNN_OK) return rc;
+    if ((rc = ix->qnorm.reserve((size_t)per_pad)) != KNN_OK) return rc;
+    if ((rc = ix->hk_a.reserve((size_t)(per * N))) != KNN_OK) return rc;
+    if ((rc = ix->hk_b.reserve((size_t)(per * N))) != KNN_OK) return rc;
+    if ((rc = ix->hk_off.reserve((size_t)per + 1)) != KNN_OK) return rc;
     const int rb = std::max(1, bits_for(N));
     const unsigned end_bit = 32u + (unsigned)rb;
     for (int64_t q0 = 0; q0 < nq; q0 += per) {
@@ -225,21 +249,11 @@ int hugek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int
         hipLaunchKernelGGL(hugek_keys_kernel, grid, dim3(256), 0, st, ix->xb, ix->xn, N, ix->dp, ix->qpad,
                            ix->qnorm, (int)qc, kmetric, rb, ix->hk_a);
         KNN_HIP(hipGetLastError());
-        KNN_HIP(sort_equal_segments(ix->hk_a, ix->hk_b, (int)qc, N, end_bit, ix->hk_off, &ix->hk_tmp,
-                                    &ix->hk_tmp_cap, false, st));
+        KNN_HIP(sort_equal_segments(ix->hk_a, ix->hk_b, (int)qc, N, end_bit, ix->hk_off, ix->hk_tmp, st));
         KNN_HIP(launch_sorted_write(ix->hk_b, N, (int)qc, k, kmetric, rb, ix->id_offset, true, D + q0 * k,
                                     I + q0 * k, st));
     }
     return KNN_OK;
-}
-
-void hugek_free(knn_index* ix) {
-    for (void* p : {(void*)ix->hk_a, (void*)ix->hk_b, (void*)ix->hk_off, ix->hk_tmp})
-        if (p) (void)hipFree(p);
-    ix->hk_a = ix->hk_b = nullptr;
-    ix->hk_off = nullptr;
-    ix->hk_tmp = nullptr;
-    ix->hk_a_cap = ix->hk_b_cap = ix->hk_off_cap = ix->hk_tmp_cap = 0;
 }
 
 // Merge of nlists sorted lists of kin entries per query into the top k (any k; labels < 2^32),
@@ -270,7 +284,8 @@ hipError_t launch_merge_huge(const float* cD, const int64_t* cI, int nlists, int
         hipLaunchKernelGGL(hugek_pack_lists_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)qc), dim3(256), 0,
                            st, cD + q0 * kin, cI + q0 * kin, nlists, kin, sd, si, metric, a);
         if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = sort_equal_segments(a, b, (int)qc, M, 64u, off, &tmp, &tmp_cap, true, st)) != hipSuccess) break;
+        if ((e = launch_offsets(off, (int)qc, M, st)) != hipSuccess) break;
+        if ((e = sort_u64_segments(a, b, qc * M, (int)qc, off, 64u, &tmp, &tmp_cap, true, st)) != hipSuccess) break;
         e = launch_sorted_write(b, M, (int)qc, k, metric, 32, (int64_t)0, false, D + q0 * k, I + q0 * k, st);
     }
     cleanup();

@@ -4,6 +4,10 @@
 // over several devices; knn_range.hip: range search; knn_filter.hip: filtered search;
 // knn_remove.hip: remove_ids).  Not part of the public ABI
 // (include/imgrec_knn.h).
+//
+// Ownership: every device or page-locked allocation the index keeps is a DevBuf / PinBuf member
+// (dev_buf.h over the two memory spaces below), released by the index's destructor; there is no
+// free list to keep in step.  The per-row corpus arrays are listed once, by corpus_columns().
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +19,7 @@
 #include <vector>
 
 #include "../../include/imgrec_knn.h"
+#include "dev_buf.h"
 #include "knn_kernels.h"
 
 namespace imgrec {
@@ -52,18 +57,30 @@ struct DeviceGuard {
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
-// Device buffer that only grows (workspace reused across searches).
-template <typename T>
-int grow(T** p, size_t* cap, size_t need) {
-    if (*cap >= need) return KNN_OK;
-    const size_t n = std::max(need, *cap * 3 / 2);
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    KNN_HIP(hipMalloc((void**)p, n * sizeof(T)));
-    *cap = n;
-    return KNN_OK;
+// The two memory spaces of dev_buf.h: device memory (regrowth reserves half as much again) and
+// page-locked host memory (exact sizes).  The only callers of hipFree / hipHostFree.
+inline int alloc_result(hipError_t e, const char* call) {
+    if (e == hipSuccess) return KNN_OK;
+    set_err("%s failed: %s", call, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? KNN_ENOMEM : KNN_EHIP;
 }
+struct DeviceSpace {
+    static constexpr bool kSlack = true;
+    static int alloc(void** p, size_t bytes) {
+        return alloc_result(hipMalloc(p, bytes), "hipMalloc((void**)p, n * sizeof(T))");
+    }
+    static void free(void* p) { (void)hipFree(p); }
+};
+struct PinnedSpace {
+    static constexpr bool kSlack = false;
+    static int alloc(void** p, size_t bytes) {
+        return alloc_result(hipHostMalloc(p, bytes, hipHostMallocDefault),
+                            "hipHostMalloc(p, need_bytes, hipHostMallocDefault)");
+    }
+    static void free(void* p) { (void)hipHostFree(p); }
+};
+template <typename T> using DevBuf = Buf<T, DeviceSpace>;
+template <typename T> using PinBuf = Buf<T, PinnedSpace>;
 
 // ---- launch geometry (knn_plan.cpp; DESIGN.md "Launch plan") ---------------------------------
 struct Plan {
@@ -96,6 +113,9 @@ int b16_km(int k);
 
 }  // namespace imgrec
 
+using imgrec::DevBuf;
+using imgrec::PinBuf;
+
 struct knn_index {
     int d = 0, dp = 0, metric = KNN_METRIC_L2, device = 0, cus = 256;
     // launch knobs read from the environment at creation (A/B and tests): the int8 scan's
@@ -125,7 +145,7 @@ struct knn_index {
     int i8_pool64 = 4;
     int i8_pool_ch = 2;
     bool i8_pool_forced = false;
-    int* i8_dyn = nullptr;      // the pool's two counters (zeroed once; the scan leaves them at 0)
+    DevBuf<int> i8_dyn;      // the pool's two counters (zeroed once; the scan leaves them at 0)
     bool stream_lists = true;   // exact lists of <= 4 queries from one fp32 stream (IMGREC_STREAM_LISTS=0: tiles)
     bool merge_single = false;  // IMGREC_MERGE_SINGLE=1: the single-level merge in the rerank
     // IMGREC_B16W_SHARED_BOUND=0: the 256 x 256 bf16 kernel's lists screen each on their own (no
@@ -137,21 +157,21 @@ struct knn_index {
     bool merge_fuse1 = true;    // IMGREC_MERGE_FUSE=1: only level 2 in the rerank (0: neither)
     int64_t ntotal = 0, cap = 0, id_offset = 0;
     bool trained = true;
-    float* xb = nullptr;     // cap x dp
-    float* xn = nullptr;     // cap
-    uint32_t* xs = nullptr;  // cap x dp split-bf16 copy (built by the first split search)
-    uint16_t* xh = nullptr;  // cap x dpb bf16 copy (b16_ok only)
-    float* xr = nullptr;     // cap: |x - bf16(x)| per row (b16_ok only)
-    int8_t* x8 = nullptr;    // cap x nblk8*64 block-scaled int8 copy (built by the first i8 search)
-    float* x8s = nullptr;    // cap x nblk8 block scales
-    float* x8r = nullptr;    // cap: |x - s c| per row
-    float* x8r_max = nullptr; size_t x8r_max_cap = 0;   // device scalar, max of x8r
+    DevBuf<float> xb;     // cap x dp
+    DevBuf<float> xn;     // cap
+    DevBuf<uint32_t> xs;  // cap x dp split-bf16 copy (built by the first split search)
+    DevBuf<uint16_t> xh;  // cap x dpb bf16 copy (b16_ok only)
+    DevBuf<float> xr;     // cap: |x - bf16(x)| per row (b16_ok only)
+    DevBuf<int8_t> x8;    // cap x nblk8*64 block-scaled int8 copy (built by the first i8 search)
+    DevBuf<float> x8s;    // cap x nblk8 block scales
+    DevBuf<float> x8r;    // cap: |x - s c| per row
+    DevBuf<float> x8r_max;   // device scalar, max of x8r
     int nblk8 = 0;           // 64-element blocks per row (d <= 4096)
-    int8_t* q8 = nullptr; size_t q8_cap = 0;        // a search's two-level query codes
-    float* q8s = nullptr; size_t q8s_cap = 0;       //   their scales
-    float* q8r = nullptr; size_t q8r_cap = 0;       //   |q - q~| per query
-    float* xn_max = nullptr; // device scalar, max |x|^2 (refreshed when rows change)
-    float* xr_max = nullptr; // device scalar, max |x - bf16(x)|
+    DevBuf<int8_t> q8;        // a search's two-level query codes
+    DevBuf<float> q8s;       //   their scales
+    DevBuf<float> q8r;       //   |q - q~| per query
+    DevBuf<float> xn_max; // device scalar, max |x|^2 (refreshed when rows change)
+    DevBuf<float> xr_max; // device scalar, max |x - bf16(x)|
     int dpb = 0;             // bf16 row stride (elements)
     bool split_ok = false, b16_ok = false, xn_max_stale = true;
     int mode = KNN_SEARCH_AUTO;
@@ -170,45 +190,43 @@ struct knn_index {
     bool fence_recorded = false;   // `fence` already marks its end
     bool fence_lazy = false;
     // search workspace
-    float* qpad = nullptr; size_t qpad_cap = 0;
-    float* qnorm = nullptr; size_t qnorm_cap = 0;
-    size_t xn_max_cap = 0;
-    float* cand_d = nullptr; size_t cand_d_cap = 0;
-    int64_t* cand_i = nullptr; size_t cand_i_cap = 0;
-    uint32_t* qsplit = nullptr; size_t qsplit_cap = 0;
-    float* cand2_d = nullptr; size_t cand2_d_cap = 0;
-    int64_t* cand2_i = nullptr; size_t cand2_i_cap = 0;
-    int* fail = nullptr; size_t fail_cap = 0;          // the uncertified queries of a chunk
-    int* chance = nullptr; size_t chance_cap = 0;      // the second-chance queue of a chunk
-    float* sc_key = nullptr; size_t sc_key_cap = 0;    // sliced second chance (RerankArgs::sc_*)
-    int64_t* sc_lab = nullptr; size_t sc_lab_cap = 0;
-    unsigned* sc_meta = nullptr; size_t sc_meta_cap = 0;
-    int* sc_done = nullptr; size_t sc_done_cap = 0;
-    int* stat = nullptr;                               // 12 ints: two chunk parities + totals
+    DevBuf<float> qpad;
+    DevBuf<float> qnorm;
+    DevBuf<float> cand_d;
+    DevBuf<int64_t> cand_i;
+    DevBuf<uint32_t> qsplit;
+    DevBuf<float> cand2_d;
+    DevBuf<int64_t> cand2_i;
+    DevBuf<int> fail;          // the uncertified queries of a chunk
+    DevBuf<int> chance;      // the second-chance queue of a chunk
+    DevBuf<float> sc_key;    // sliced second chance (RerankArgs::sc_*)
+    DevBuf<int64_t> sc_lab;
+    DevBuf<unsigned> sc_meta;
+    DevBuf<int> sc_done;
+    DevBuf<int> stat;                               // 12 ints: two chunk parities + totals
     int stat_seq = 0;                                  // chunks run (parity = seq & 1)
     bool stat_valid = false;                           // the last search ran a candidate path
-    uint16_t* qb16 = nullptr; size_t qb16_cap = 0;
-    float* q_resid = nullptr; size_t q_resid_cap = 0;
-    float* floor = nullptr; size_t floor_cap = 0;
-    float* heads = nullptr; size_t heads_cap = 0;       // int8 lists' first keys (direct route)
-    float* mws_d = nullptr; size_t mws_d_cap = 0;          // two-level candidate merge workspace
-    int64_t* mws_i = nullptr; size_t mws_i_cap = 0;
-    float* mws_f = nullptr; size_t mws_f_cap = 0;
-    uint32_t* sbound = nullptr; size_t sbound_cap = 0;       // shared screen bound records (kSBWords per query)
-    size_t xr_max_cap = 0;
+    DevBuf<uint16_t> qb16;
+    DevBuf<float> q_resid;
+    DevBuf<float> floor;
+    DevBuf<float> heads;       // int8 lists' first keys (direct route)
+    DevBuf<float> mws_d;          // two-level candidate merge workspace
+    DevBuf<int64_t> mws_i;
+    DevBuf<float> mws_f;
+    DevBuf<uint32_t> sbound;       // shared screen bound records (kSBWords per query)
     // exact re-run workspace (device-planned: queries, candidate lists, plan)
-    float* fb_q = nullptr; size_t fb_q_cap = 0;
-    float* fb_qn = nullptr; size_t fb_qn_cap = 0;
-    float* fb_cd = nullptr; size_t fb_cd_cap = 0;
-    int64_t* fb_ci = nullptr; size_t fb_ci_cap = 0;
-    int* tail_ctl = nullptr; size_t tail_ctl_cap = 0;   // tail claim counters + block tickets
+    DevBuf<float> fb_q;
+    DevBuf<float> fb_qn;
+    DevBuf<float> fb_cd;
+    DevBuf<int64_t> fb_ci;
+    DevBuf<int> tail_ctl;   // tail claim counters + block tickets
     // host-path staging (device side), and page-locked host buffers for small searches
-    float* pq = nullptr; size_t pq_cap = 0;        // hipHostMalloc'ed (caps in bytes)
-    float* pd = nullptr; size_t pd_cap = 0;
-    int64_t* pi = nullptr; size_t pi_cap = 0;
-    float* hq = nullptr; size_t hq_cap = 0;
-    float* hd = nullptr; size_t hd_cap = 0;
-    int64_t* hi = nullptr; size_t hi_cap = 0;
+    PinBuf<float> pq;
+    PinBuf<float> pd;
+    PinBuf<int64_t> pi;
+    DevBuf<float> hq;
+    DevBuf<float> hd;
+    DevBuf<int64_t> hi;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> ev;   // pairs
@@ -216,52 +234,52 @@ struct knn_index {
     // one index over several devices (knn_multi.cpp); NULL for a single-device index
     struct knn_multi* multi = nullptr;
     // k > KNN_MAX_K (knn_largek.hip): the fallback's stripe lists, the uncertified queries (+ count)
-    uint64_t* lk_run = nullptr; size_t lk_run_cap = 0;
+    DevBuf<uint64_t> lk_run;
     // a chunk's failed queries, then their count and the last large-k search's total (device)
-    int* lk_fail = nullptr; size_t lk_fail_cap = 0;
+    DevBuf<int> lk_fail;
     // k > KNN_MAX_K_LARGE (knn_hugek.hip): a query chunk's keys, sorted keys, segment offsets, and
     // the sort's temporary storage (bytes)
-    uint64_t* hk_a = nullptr; size_t hk_a_cap = 0;
-    uint64_t* hk_b = nullptr; size_t hk_b_cap = 0;
-    unsigned* hk_off = nullptr; size_t hk_off_cap = 0;
-    void* hk_tmp = nullptr; size_t hk_tmp_cap = 0;
+    DevBuf<uint64_t> hk_a;
+    DevBuf<uint64_t> hk_b;
+    DevBuf<unsigned> hk_off;
+    DevBuf<char> hk_tmp;
     // range search (knn_range.hip): the append buffer (entries + their queries; starts at
     // range_cap0 entries, IMGREC_RANGE_CAP, and grows to a chunk's total when that overflows it),
     // the entries scattered into query segments, per-query counts, segment offsets, scatter
     // cursors, and the chunk's total on the device and in page-locked host memory
     size_t range_cap0 = size_t(1) << 20;
-    uint64_t* rg_ent = nullptr; size_t rg_ent_cap = 0;
-    uint32_t* rg_entq = nullptr; size_t rg_entq_cap = 0;
-    uint64_t* rg_seg = nullptr; size_t rg_seg_cap = 0;
-    uint32_t* rg_cnt = nullptr; size_t rg_cnt_cap = 0;
-    uint32_t* rg_off = nullptr; size_t rg_off_cap = 0;
-    uint32_t* rg_cur = nullptr; size_t rg_cur_cap = 0;
-    unsigned long long* rg_total = nullptr; size_t rg_total_cap = 0;
-    unsigned long long* rg_total_h = nullptr;
+    DevBuf<uint64_t> rg_ent;
+    DevBuf<uint32_t> rg_entq;
+    DevBuf<uint64_t> rg_seg;
+    DevBuf<uint32_t> rg_cnt;
+    DevBuf<uint32_t> rg_off;
+    DevBuf<uint32_t> rg_cur;
+    DevBuf<unsigned long long> rg_total;
+    PinBuf<unsigned long long> rg_total_h;
     // filtered search (knn_filter.hip): the compacted list of the selected rows (padded to a whole
     // tile), the compaction's per-block counts / offsets, the selected count on the device and in
     // page-locked host memory (read by the k > KNN_MAX_K route only), and the host form's device
     // copy of the bitmap
-    uint32_t* ft_list = nullptr; size_t ft_list_cap = 0;
-    uint32_t* ft_blk = nullptr; size_t ft_blk_cap = 0;
-    uint32_t* ft_m = nullptr; size_t ft_m_cap = 0;
-    uint32_t* ft_m_h = nullptr;
-    uint8_t* ft_bits = nullptr; size_t ft_bits_cap = 0;
+    DevBuf<uint32_t> ft_list;
+    DevBuf<uint32_t> ft_blk;
+    DevBuf<uint32_t> ft_m;
+    PinBuf<uint32_t> ft_m_h;
+    DevBuf<uint8_t> ft_bits;
     // remove_ids (knn_remove.hip): rows per bounce chunk when > 0 (IMGREC_REMOVE_CHUNK, tests), the
     // survivor count and first moved row in page-locked host memory, and a shard's copy of the
     // bitmap's per-word popcount prefix (multi-device renumbering)
     int64_t remove_chunk = 0;
-    uint32_t* rm_h = nullptr;
-    uint32_t* rm_pref = nullptr; size_t rm_pref_cap = 0;
+    PinBuf<uint32_t> rm_h;
+    DevBuf<uint32_t> rm_pref;
 };
 
 // One range search's result (knn_range_search): buffers on `device`, complete once `done` fires.
 struct knn_range_result {
     int device = 0;
     int64_t nq = 0, size = 0;
-    int64_t* lims = nullptr;     // nq + 1
-    float* D = nullptr;          // size (one unused element when empty)
-    int64_t* I = nullptr;
+    DevBuf<int64_t> lims;        // nq + 1
+    DevBuf<float> D;             // size (one unused element when empty)
+    DevBuf<int64_t> I;
     hipEvent_t done = nullptr;
 };
 
@@ -274,6 +292,12 @@ int set_trained(knn_index* ix, bool trained);
 int fence_begin(knn_index* ix, hipStream_t st);
 int fence_end(knn_index* ix, hipStream_t st);
 int fence_end_synced(knn_index* ix);
+// The per-row corpus arrays with their row strides in bytes, in allocation order: the only place
+// that lists them.  Fills cols with the live ones (the split and int8 copies once materialised, the
+// bf16 copy where enabled: what follows every add, regrowth and removal) and returns their number;
+// all = true: with every column, at its kCol index.
+enum { kColXb, kColXn, kColXs, kColXh, kColXr, kColX8, kColX8s, kColX8r, kCorpusColumns };
+int corpus_columns(knn_index* ix, Column<DeviceSpace>* cols, bool all = false);
 int reserve_rows(knn_index* ix, int64_t need, hipStream_t st);
 int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st);
 int ensure_split(knn_index* ix, hipStream_t st);
@@ -302,7 +326,6 @@ bool stream_lists_ok(const knn_index* ix, int64_t nq);
 int stream_splits(const knn_index* ix);
 hipError_t launch_stream_lists(const knn_index* ix, const float* qpad, const float* qnorm, int64_t nq,
                                int metric, int sp, float* cd, int64_t* ci, hipStream_t st);
-void largek_free(knn_index* ix);
 // queries the last large-k search sent to the exact scan (a device count; waits for the index)
 int largek_fallbacks(knn_index* ix, int64_t* n);
 // merge of nlists sorted per-shard lists for KNN_MAX_K < k (nlists * kin <= 8192; labels < 2^32)
@@ -313,7 +336,13 @@ bool use_split(const knn_index* ix, int64_t nq, int k);
 // knn_hugek.hip: k > KNN_MAX_K_LARGE — every (query, row) key, a segmented sort per query
 int hugek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                  hipStream_t st);
-void hugek_free(knn_index* ix);
+// its segmented sort (knn_kernels.h) on an index's own temporary storage, which grows to what the
+// sort asks for; and the same for nseg equal segments of `seg` keys, whose offsets it writes into
+// `off` (nseg + 1 entries) first
+hipError_t sort_u64_segments(uint64_t* in, uint64_t* out, int64_t total, int nseg, const unsigned* off,
+                             unsigned end_bit, DevBuf<char>& tmp, hipStream_t st);
+hipError_t sort_equal_segments(uint64_t* in, uint64_t* out, int nseg, int64_t seg, unsigned end_bit,
+                               unsigned* off, DevBuf<char>& tmp, hipStream_t st);
 // merge of nlists sorted lists of kin entries per query for any k (labels < 2^32)
 hipError_t launch_merge_huge(const float* cD, const int64_t* cI, int nlists, int64_t nq, int kin,
                              int64_t sd, int64_t si, int k, int metric, float* D, int64_t* I,
@@ -330,13 +359,11 @@ int range_search_locked(knn_index* ix, const float* q, int64_t nq, float radius,
 int range_result_from_host(int device, int64_t nq, const int64_t* lims, const float* D, const int64_t* I,
                            hipStream_t st, knn_range_result** out);
 void range_result_free(knn_range_result* r);
-void range_free(knn_index* ix);
 // knn_filter.hip: the k best rows among those the bitmap selects (device bitmap, IDSelectorBitmap
 // layout; bit lmap[r] for local row r when lmap is given, a shard's local -> global map), for the
 // nq device queries on `st`; labels are row + id_offset.  Waits once only when k > KNN_MAX_K.
 int filtered_search_locked(knn_index* ix, const float* q, int64_t nq, int k, const uint8_t* bits,
                            int64_t nbits, const int64_t* lmap, float* D, int64_t* I, hipStream_t st);
-void filter_free(knn_index* ix);
 // its compaction alone: ft_list = the ascending local rows whose bit is set (invert: the stored rows
 // whose bit is clear), padded with row 0 to 256 entries, and ft_m[0] = their count
 int compact_rows(knn_index* ix, const uint8_t* bits, int64_t nbits, const int64_t* lmap, bool invert,
@@ -350,6 +377,5 @@ int remove_rows_locked(knn_index* ix, const uint8_t* bits, int64_t nbits, const 
 // their exclusive popcount prefix; removed: every set bit)
 hipError_t launch_renumber_labels(int64_t* lab, int64_t n, const uint32_t* words, const uint32_t* pref,
                                   int64_t nbits, int64_t removed, hipStream_t st);
-void remove_free(knn_index* ix);
 
 }  // namespace imgrec

@@ -329,15 +329,10 @@ hipError_t launch_max_norm(const float* xn, int64_t n, float* out, hipStream_t s
 
 // IVF-PQ (ivfpq.hip; layouts in include/imgrec_ivfpq.h)
 // segmented radix sort of u64 keys (knn_hugek.hip, rocPRIM): segment i = [off[i], off[i + 1]) of
-// `total` (< 2^32) keys over bits [0, end_bit); the temporary storage grows in *tmp (hipMallocAsync
-// on st when async_tmp)
+// `total` (< 2^32) keys over bits [0, end_bit); the temporary storage grows in *tmp by
+// hipMallocAsync on st (async_tmp must be true; an index's own storage: the overloads in knn_index.h)
 hipError_t sort_u64_segments(uint64_t* in, uint64_t* out, int64_t total, int nseg, const unsigned* off,
                              unsigned end_bit, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st);
-// the same for nseg equal segments of `seg` keys in `in` -> `out`: writes their offsets into `off`
-// (nseg + 1 entries) first.  The temporary storage grows by hipMalloc (an index's workspace), or in
-// stream order when `async_tmp` (a merge's, freed by the caller with hipFreeAsync)
-hipError_t sort_equal_segments(uint64_t* in, uint64_t* out, int nseg, int64_t seg, unsigned end_bit,
-                               unsigned* off, void** tmp, size_t* tmp_cap, bool async_tmp, hipStream_t st);
 // row q of D / I (k entries) from the first min(k, seg) sorted values (key bits << rb | label) of
 // segment q, padded past them and from the first ~0 (empty) value on; label_is_row adds id_offset
 hipError_t launch_sorted_write(const uint64_t* sorted, int64_t seg, int nq, int k, int metric, int rb,

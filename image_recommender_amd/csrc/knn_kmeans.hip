@@ -430,21 +430,22 @@ kmeans_gather_kernel(const float* __restrict__ src, int d, const int64_t* __rest
 // ---- host side ----------------------------------------------------------------------------------
 
 // One workspace per device, shared by every call on it: calls hold `mu` while they enqueue, and a
-// call on another stream than the previous one first waits for that call's event.
+// call on another stream than the previous one first waits for that call's event.  It lives as
+// long as the process (never deleted: its buffers go with the process).
 struct Workspace {
     std::mutex mu;
     hipEvent_t done = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
-    float* cnorm = nullptr; size_t cnorm_cap = 0;
-    double* partial = nullptr; size_t partial_cap = 0;
-    uint32_t* skey = nullptr; size_t skey_cap = 0;
-    uint32_t* sidx = nullptr; size_t sidx_cap = 0;
-    uint32_t* off = nullptr; size_t off_cap = 0;
-    uint32_t* pstart = nullptr; size_t pstart_cap = 0;
-    float* psum = nullptr; size_t psum_cap = 0;
-    int* pairs = nullptr; size_t pairs_cap = 0;
-    char* tmp = nullptr; size_t tmp_cap = 0;
+    DevBuf<float> cnorm;
+    DevBuf<double> partial;
+    DevBuf<uint32_t> skey;
+    DevBuf<uint32_t> sidx;
+    DevBuf<uint32_t> off;
+    DevBuf<uint32_t> pstart;
+    DevBuf<float> psum;
+    DevBuf<int> pairs;
+    DevBuf<char> tmp;
 };
 
 Workspace* workspace(int device) {
@@ -499,21 +500,21 @@ int step_locked(Workspace* w, const float* x, int64_t n, int d, const float* c, 
     const int64_t maxparts = (n + P - 1) / P + k;
     if (maxparts >= (int64_t(1) << 31)) KNN_FAIL(KNN_EINVAL, "kmeans_step_device: too many parts (%lld)", (long long)maxparts);
     int rc;
-    if ((rc = grow(&w->cnorm, &w->cnorm_cap, (size_t)k)) != KNN_OK) return rc;
-    if ((rc = grow(&w->partial, &w->partial_cap, (size_t)nblk)) != KNN_OK) return rc;
-    if ((rc = grow(&w->skey, &w->skey_cap, (size_t)n)) != KNN_OK) return rc;
-    if ((rc = grow(&w->sidx, &w->sidx_cap, (size_t)n)) != KNN_OK) return rc;
-    if ((rc = grow(&w->off, &w->off_cap, (size_t)k + 1)) != KNN_OK) return rc;
-    if ((rc = grow(&w->pstart, &w->pstart_cap, (size_t)k + 1)) != KNN_OK) return rc;
-    if ((rc = grow(&w->psum, &w->psum_cap, (size_t)maxparts * d)) != KNN_OK) return rc;
+    if ((rc = w->cnorm.reserve((size_t)k)) != KNN_OK) return rc;
+    if ((rc = w->partial.reserve((size_t)nblk)) != KNN_OK) return rc;
+    if ((rc = w->skey.reserve((size_t)n)) != KNN_OK) return rc;
+    if ((rc = w->sidx.reserve((size_t)n)) != KNN_OK) return rc;
+    if ((rc = w->off.reserve((size_t)k + 1)) != KNN_OK) return rc;
+    if ((rc = w->pstart.reserve((size_t)k + 1)) != KNN_OK) return rc;
+    if ((rc = w->psum.reserve((size_t)maxparts * d)) != KNN_OK) return rc;
     unsigned end_bit = 1;
     while (end_bit < 31 && (1u << end_bit) < (unsigned)k) ++end_bit;
     const uint32_t* keys_in = reinterpret_cast<const uint32_t*>(assign);
     rocprim::counting_iterator<uint32_t> iota(0u);
     size_t need = 0;
-    KNN_HIP(rocprim::radix_sort_pairs(nullptr, need, keys_in, w->skey, iota, w->sidx, (unsigned)n, 0u,
-                                      end_bit, st));
-    if ((rc = grow(&w->tmp, &w->tmp_cap, std::max(need, size_t(16)))) != KNN_OK) return rc;
+    KNN_HIP(rocprim::radix_sort_pairs(nullptr, need, keys_in, w->skey.get(), iota, w->sidx.get(),
+                                      (unsigned)n, 0u, end_bit, st));
+    if ((rc = w->tmp.reserve(std::max(need, size_t(16)))) != KNN_OK) return rc;
 
     if (ev) KNN_HIP(hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(kmeans_norms_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, c, k, d, w->cnorm);
@@ -526,9 +527,9 @@ int step_locked(Workspace* w, const float* x, int64_t n, int d, const float* c, 
     KNN_HIP(hipGetLastError());
     if (ev) KNN_HIP(hipEventRecord(ev[1], st));
 
-    size_t have = w->tmp_cap;
-    KNN_HIP(rocprim::radix_sort_pairs(w->tmp, have, keys_in, w->skey, iota, w->sidx, (unsigned)n, 0u,
-                                      end_bit, st));
+    size_t have = w->tmp.cap();
+    KNN_HIP(rocprim::radix_sort_pairs(w->tmp.get(), have, keys_in, w->skey.get(), iota, w->sidx.get(),
+                                      (unsigned)n, 0u, end_bit, st));
     hipLaunchKernelGGL(kmeans_offsets_kernel, dim3((unsigned)((k + 1 + 255) / 256)), dim3(256), 0, st,
                        w->skey, (uint32_t)n, k, w->off, counts);
     KNN_HIP(hipGetLastError());
@@ -585,7 +586,7 @@ int split_locked(Workspace* w, float* c, int k, int d, int64_t* cnt, int* nsplit
     const int np = (int)(pairs.size() / 2);
     if (nsplit) *nsplit = np;
     if (np == 0) return KNN_OK;
-    if ((rc = grow(&w->pairs, &w->pairs_cap, pairs.size())) != KNN_OK) return rc;
+    if ((rc = w->pairs.reserve(pairs.size())) != KNN_OK) return rc;
     // the list must have left `pairs` before it goes out of scope: the one wait of a repair
     KNN_HIP(hipMemcpyAsync(w->pairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice, st));
     KNN_HIP(hipStreamSynchronize(st));
@@ -604,10 +605,6 @@ int check_train_args(const void* x, int64_t n, int d, int k, const kmeans_params
     return KNN_OK;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
 struct StreamGuard {
     hipStream_t s = nullptr;
     ~StreamGuard() {
@@ -629,16 +626,19 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
     KNN_HIP(hipGetDevice(&device));
     Workspace* w = workspace(device);
     const size_t kd = (size_t)k * d;
-    DevBuf ca, cb, as, di, cn, ob, rows;
-    KNN_HIP(hipMalloc(&ca.p, kd * sizeof(float)));
-    KNN_HIP(hipMalloc(&cb.p, kd * sizeof(float)));
-    KNN_HIP(hipMalloc(&as.p, (size_t)n * sizeof(int32_t)));
-    KNN_HIP(hipMalloc(&di.p, (size_t)n * sizeof(float)));
-    KNN_HIP(hipMalloc(&cn.p, ((size_t)k + 1) * sizeof(int64_t)));     // counts, then the objective
-    if (!init) KNN_HIP(hipMalloc(&rows.p, (size_t)k * sizeof(int64_t)));
+    DevBuf<float> ca, cb, di;
+    DevBuf<int32_t> as;
+    DevBuf<int64_t> cn, rows;
+    int rc;
+    if ((rc = ca.reserve(kd)) != KNN_OK) return rc;
+    if ((rc = cb.reserve(kd)) != KNN_OK) return rc;
+    if ((rc = as.reserve((size_t)n)) != KNN_OK) return rc;
+    if ((rc = di.reserve((size_t)n)) != KNN_OK) return rc;
+    if ((rc = cn.reserve((size_t)k + 1)) != KNN_OK) return rc;      // counts, then the objective
+    if (!init && (rc = rows.reserve((size_t)k)) != KNN_OK) return rc;
     Events evs;
     for (hipEvent_t& e : evs.e) KNN_HIP(hipEventCreate(&e));
-    int64_t* cnt_d = (int64_t*)cn.p;
+    int64_t* cnt_d = cn;
     double* obj_d = (double*)(cnt_d + k);
     std::vector<int64_t> host((size_t)k + 1);
     std::vector<double> stats((size_t)prm->niter * KMEANS_STATS_PER_ITER), best_stats;
@@ -647,8 +647,8 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
     const int flags = prm->spherical ? KMEANS_SPHERICAL : 0;
 
     for (int redo = 0; redo < prm->nredo; ++redo) {
-        float* cur = (float*)ca.p;
-        float* nxt = (float*)cb.p;
+        float* cur = ca;
+        float* nxt = cb;
         {
             std::lock_guard<std::mutex> lk(w->mu);
             int rc = ws_begin(w, st);
@@ -666,10 +666,10 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
                     if (v == j) seen.insert(j);
                     pick.push_back(v);
                 }
-                KNN_HIP(hipMemcpyAsync(rows.p, pick.data(), (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, st));
+                KNN_HIP(hipMemcpyAsync(rows, pick.data(), (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, st));
                 KNN_HIP(hipStreamSynchronize(st));
                 hipLaunchKernelGGL(kmeans_gather_kernel, dim3((unsigned)k), dim3(256), 0, st, x, d,
-                                   (const int64_t*)rows.p, cur);
+                                   rows, cur);
                 KNN_HIP(hipGetLastError());
             }
             if (prm->spherical) {
@@ -687,7 +687,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
                 std::lock_guard<std::mutex> lk(w->mu);
                 int rc = ws_begin(w, st);
                 if (rc != KNN_OK) return rc;
-                if ((rc = step_locked(w, x, n, d, cur, k, flags, (int32_t*)as.p, (float*)di.p, nxt, cnt_d, obj_d,
+                if ((rc = step_locked(w, x, n, d, cur, k, flags, as, di, nxt, cnt_d, obj_d,
                                       st, evs.e)) != KNN_OK)
                     return rc;
                 KNN_HIP(hipMemcpyAsync(host.data(), cnt_d, ((size_t)k + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -818,12 +818,12 @@ int kmeans_train(const float* x_host, int64_t n, int d, int k, const kmeans_para
     KNN_HIP(hipGetDeviceCount(&ndev));
     if (params->device >= ndev) KNN_FAIL(KNN_EINVAL, "kmeans_train: device %d out of range (%d visible)", params->device, ndev);
     DeviceGuard g(params->device);
-    DevBuf xd;
-    KNN_HIP(hipMalloc(&xd.p, (size_t)n * d * sizeof(float)));
+    DevBuf<float> xd;
+    if ((rc = xd.reserve((size_t)n * d)) != KNN_OK) return rc;
     StreamGuard sg;       // declared after xd: the stream is drained before the rows are freed
     KNN_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    KNN_HIP(hipMemcpyAsync(xd.p, x_host, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, sg.s));
-    return train_device_impl((const float*)xd.p, n, d, k, params, init_centroids, centroids_out, obj_out,
+    KNN_HIP(hipMemcpyAsync(xd, x_host, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, sg.s));
+    return train_device_impl(xd, n, d, k, params, init_centroids, centroids_out, obj_out,
                              stats_out, sg.s);
 }
 

@@ -500,13 +500,6 @@ int largek_fallbacks(knn_index* ix, int64_t* n) {
     return KNN_OK;
 }
 
-void largek_free(knn_index* ix) {
-    for (void* p : {(void*)ix->lk_run, (void*)ix->lk_fail})
-        if (p) (void)hipFree(p);
-    ix->lk_run = nullptr;
-    ix->lk_fail = nullptr;
-}
-
 int largek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                   hipStream_t st) {
     const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
@@ -522,9 +515,9 @@ int largek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
     const int S = (int)std::max<int64_t>(1, std::min<int64_t>({64, kLKM / k, (ix->ntotal + 1023) / 1024}));
     const int64_t R = (ix->ntotal + S - 1) / S;
     const int64_t chunk = std::min<int64_t>(kLKChunk, nq);
-    if ((rc = grow(&ix->lk_run, &ix->lk_run_cap, (size_t)chunk * S * k)) != KNN_OK) return rc;
+    if ((rc = ix->lk_run.reserve((size_t)chunk * S * k)) != KNN_OK) return rc;
     // lk_fail: a chunk's failed queries [0, kLKChunk), their count, the search's total
-    if ((rc = grow(&ix->lk_fail, &ix->lk_fail_cap, (size_t)kLKChunk + 2)) != KNN_OK) return rc;
+    if ((rc = ix->lk_fail.reserve((size_t)kLKChunk + 2)) != KNN_OK) return rc;
     int* cnt = ix->lk_fail + kLKChunk;
     KNN_HIP(hipMemsetAsync(cnt + 1, 0, sizeof(int), st));
     for (int64_t q0 = 0; q0 < nq; q0 += kLKChunk) {
@@ -535,10 +528,10 @@ int largek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
         const bool stream = stream_lists_ok(ix, qc);
         const int sp = stream_splits(ix);
         const size_t ncap = std::max<size_t>((size_t)p.ncand, (size_t)sp * KNN_MAX_K);
-        if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->qnorm, &ix->qnorm_cap, (size_t)p.nq_pad)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)qc * ncap)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)qc * ncap)) != KNN_OK) return rc;
+        if ((rc = ix->qpad.reserve((size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
+        if ((rc = ix->qnorm.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
+        if ((rc = ix->cand_d.reserve((size_t)qc * ncap)) != KNN_OK) return rc;
+        if ((rc = ix->cand_i.reserve((size_t)qc * ncap)) != KNN_OK) return rc;
         KNN_HIP(launch_rows_ingest(q + q0 * ix->d, qc, ix->d, ix->dp, p.nq_pad,
                                    ix->metric == KNN_METRIC_COSINE ? 1 : 0, ix->qpad, ix->qnorm, st));
         int nlists = p.ncand / p.km, ncand = p.ncand;

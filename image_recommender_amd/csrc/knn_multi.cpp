@@ -26,25 +26,22 @@ struct knn_multi {
     std::vector<int> devices;
     struct Run { int64_t g0; int shard; int64_t l0; int64_t n; };
     std::vector<Run> runs;                       // global row ranges in increasing order
-    std::vector<int64_t*> lmap;                  // per shard (its device): local row -> label
-    std::vector<size_t> lmap_cap;
-    std::vector<float*> sq;                      // per shard: query copy (other devices only)
-    std::vector<size_t> sq_cap;
-    std::vector<float*> sd;                      // per shard: results (other devices only)
-    std::vector<size_t> sd_cap;
-    std::vector<int64_t*> si;
-    std::vector<size_t> si_cap;
-    std::vector<uint8_t*> sb;                    // per shard: bitmap copy (other devices only)
-    std::vector<size_t> sb_cap;
-    std::vector<float*> sx;                      // per shard: row staging for add_device
-    std::vector<size_t> sx_cap;
-    std::vector<hipEvent_t> done;                // per shard (its device)
+    struct Shard {                               // per shard, on its device
+        DevBuf<int64_t> lmap;                    // local row -> label
+        DevBuf<float> sq;                        // query copy (other devices only)
+        DevBuf<float> sd;                        // results (other devices only)
+        DevBuf<int64_t> si;
+        DevBuf<uint8_t> sb;                      // bitmap copy (other devices only)
+        DevBuf<float> sx;                        // row staging for add_device
+        hipEvent_t done = nullptr;
+    };
+    std::vector<Shard> per;
     hipEvent_t ready = nullptr;                  // inputs ready on the first device
     // IMGREC_MULTI_FORCE_REMOTE=1 (tests): shards on the first device take the other devices'
     // staging + peer-copy path too, so one GPU exercises it
     bool force_remote = false;
-    float* gD = nullptr; size_t gD_cap = 0;      // [ndev][nq][k] on the first device
-    int64_t* gI = nullptr; size_t gI_cap = 0;
+    DevBuf<float> gD;                            // [ndev][nq][k] on the first device
+    DevBuf<int64_t> gI;
 };
 
 namespace imgrec {
@@ -57,22 +54,17 @@ knn_multi* M(const knn_index* ix) { return ix->multi; }
 inline int64_t piece0(int64_t n, int s, int ndev) { return n * s / ndev; }
 
 // a label map that keeps its entries when it grows
-int grow_keep(int64_t** p, size_t* cap, size_t need, hipStream_t st) {
-    if (*cap >= need) return KNN_OK;
-    const size_t n = std::max(need, *cap * 3 / 2);
-    int64_t* np = nullptr;
-    KNN_HIP(hipMalloc((void**)&np, n * sizeof(int64_t)));
-    if (*p) {
-        const hipError_t e = hipMemcpyAsync(np, *p, *cap * sizeof(int64_t), hipMemcpyDeviceToDevice, st);
+int grow_keep(DevBuf<int64_t>& b, size_t need, hipStream_t st) {
+    if (b.cap() >= need) return KNN_OK;
+    DevBuf<int64_t> nb;
+    const int rc = nb.reserve(std::max(need, b.cap() * 3 / 2));
+    if (rc != KNN_OK) return rc;
+    if (b) {
+        const hipError_t e = hipMemcpyAsync(nb, b, b.cap() * sizeof(int64_t), hipMemcpyDeviceToDevice, st);
         const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(st) : e;
-        if (e2 != hipSuccess) {
-            (void)hipFree(np);
-            KNN_FAIL(KNN_EHIP, "label map regrowth failed: %s", hipGetErrorString(e2));
-        }
-        (void)hipFree(*p);
+        if (e2 != hipSuccess) KNN_FAIL(KNN_EHIP, "label map regrowth failed: %s", hipGetErrorString(e2));
     }
-    *p = np;
-    *cap = n;
+    b.swap(nb);                                  // (the old map goes with nb)
     return KNN_OK;
 }
 
@@ -87,9 +79,9 @@ int append_runs(knn_index* ix, const std::vector<int64_t>& before, int64_t n) {
         DeviceGuard g(sh->device);
         int rc;
         // lmap grows with the shard's capacity; rows already mapped keep their labels
-        if ((rc = grow_keep(&m->lmap[s], &m->lmap_cap[s], (size_t)sh->cap, sh->stream)) != KNN_OK)
+        if ((rc = grow_keep(m->per[s].lmap, (size_t)sh->cap, sh->stream)) != KNN_OK)
             return rc;
-        KNN_HIP(launch_iota64(m->lmap[s] + before[s], r1 - r0, ix->ntotal + r0, sh->stream));
+        KNN_HIP(launch_iota64(m->per[s].lmap + before[s], r1 - r0, ix->ntotal + r0, sh->stream));
         KNN_HIP(hipStreamSynchronize(sh->stream));
     }
     ix->ntotal += n;
@@ -113,19 +105,7 @@ int multi_create(int d, int metric, const int* devices, int ndev, knn_index** ou
     ix->multi = m;
     m->devices.assign(devices, devices + ndev);
     if (const char* e = std::getenv("IMGREC_MULTI_FORCE_REMOTE")) m->force_remote = std::atoi(e) != 0;
-    m->lmap.assign(ndev, nullptr);
-    m->lmap_cap.assign(ndev, 0);
-    m->sq.assign(ndev, nullptr);
-    m->sq_cap.assign(ndev, 0);
-    m->sd.assign(ndev, nullptr);
-    m->sd_cap.assign(ndev, 0);
-    m->si.assign(ndev, nullptr);
-    m->si_cap.assign(ndev, 0);
-    m->sb.assign(ndev, nullptr);
-    m->sb_cap.assign(ndev, 0);
-    m->sx.assign(ndev, nullptr);
-    m->sx_cap.assign(ndev, 0);
-    m->done.assign(ndev, nullptr);
+    m->per.resize(ndev);
     {
         DeviceGuard g(ix->device);
         if (hipEventCreateWithFlags(&m->ready, hipEventDisableTiming) != hipSuccess) {
@@ -141,7 +121,7 @@ int multi_create(int d, int metric, const int* devices, int ndev, knn_index** ou
         }
         m->shards.push_back(sh);
         DeviceGuard g(devices[s]);
-        if (hipEventCreateWithFlags(&m->done[s], hipEventDisableTiming) != hipSuccess) {
+        if (hipEventCreateWithFlags(&m->per[s].done, hipEventDisableTiming) != hipSuccess) {
             multi_free(ix);
             KNN_FAIL(KNN_EHIP, "hipEventCreate failed");
         }
@@ -163,19 +143,15 @@ int multi_free(knn_index* ix) {
     for (size_t s = 0; s < m->devices.size(); ++s) {
         DeviceGuard g(m->devices[s]);
         (void)hipDeviceSynchronize();
-        for (void* p : {(void*)m->lmap[s], (void*)m->sq[s], (void*)m->sd[s], (void*)m->si[s],
-                        (void*)m->sx[s], (void*)m->sb[s]})
-            if (p) (void)hipFree(p);
-        if (m->done[s]) (void)hipEventDestroy(m->done[s]);
+        if (m->per[s].done) (void)hipEventDestroy(m->per[s].done);
+        m->per[s] = knn_multi::Shard();          // (its buffers, while the guard holds)
     }
     for (knn_index* sh : m->shards) free_single(sh);
     {
         DeviceGuard g(ix->device);
-        if (m->gD) (void)hipFree(m->gD);
-        if (m->gI) (void)hipFree(m->gI);
         if (m->ready) (void)hipEventDestroy(m->ready);
+        delete m;                                // (the gather buffers, while the guard holds)
     }
-    delete m;
     ix->multi = nullptr;
     free_single(ix);
     return KNN_OK;
@@ -230,13 +206,13 @@ int multi_add_device(knn_index* ix, const float* x, int64_t n, hipStream_t st) {
         }
         DeviceGuard g(sh->device);
         const size_t bytes = (size_t)(r1 - r0) * ix->d * sizeof(float);
-        if ((rc = grow(&m->sx[s], &m->sx_cap[s], (size_t)(r1 - r0) * ix->d)) != KNN_OK) return rc;
+        if ((rc = m->per[s].sx.reserve((size_t)(r1 - r0) * ix->d)) != KNN_OK) return rc;
         KNN_HIP(hipStreamWaitEvent(sh->stream, m->ready, 0));
-        KNN_HIP(hipMemcpyPeerAsync(m->sx[s], sh->device, src, ix->device, bytes, sh->stream));
-        if ((rc = knn_add_device(sh, m->sx[s], r1 - r0, sh->stream)) != KNN_OK) return rc;
+        KNN_HIP(hipMemcpyPeerAsync(m->per[s].sx, sh->device, src, ix->device, bytes, sh->stream));
+        if ((rc = knn_add_device(sh, m->per[s].sx, r1 - r0, sh->stream)) != KNN_OK) return rc;
         // the caller may reuse x once its stream passes this point
-        KNN_HIP(hipEventRecord(m->done[s], sh->stream));
-        KNN_HIP(hipStreamWaitEvent(st, m->done[s], 0));
+        KNN_HIP(hipEventRecord(m->per[s].done, sh->stream));
+        KNN_HIP(hipStreamWaitEvent(st, m->per[s].done, 0));
     }
     return append_runs(ix, before, n);
 }
@@ -286,14 +262,15 @@ int multi_remove_ids(knn_index* ix, const uint8_t* bitmap, int64_t nbits, int64_
         std::lock_guard<std::mutex> lks(sh->mu);
         const hipStream_t ss = sh->stream;
         if ((rc = fence_begin(sh, ss)) != KNN_OK) return rc;
-        if ((rc = grow(&sh->ft_bits, &sh->ft_bits_cap, nw * 4)) != KNN_OK) return rc;
-        if ((rc = grow(&sh->rm_pref, &sh->rm_pref_cap, nw)) != KNN_OK) return rc;
+        if ((rc = sh->ft_bits.reserve(nw * 4)) != KNN_OK) return rc;
+        if ((rc = sh->rm_pref.reserve(nw)) != KNN_OK) return rc;
         KNN_HIP(hipMemcpyAsync(sh->ft_bits, words.data(), nw * 4, hipMemcpyHostToDevice, ss));
         KNN_HIP(hipMemcpyAsync(sh->rm_pref, pref.data(), nw * 4, hipMemcpyHostToDevice, ss));
         int64_t gone = 0;
-        if ((rc = remove_rows_locked(sh, sh->ft_bits, nbits, m->lmap[s], m->lmap[s], ss, &gone)) != KNN_OK)
+        if ((rc = remove_rows_locked(sh, sh->ft_bits, nbits, m->per[s].lmap, m->per[s].lmap, ss, &gone)) != KNN_OK)
             return rc;
-        KNN_HIP(launch_renumber_labels(m->lmap[s], sh->ntotal, reinterpret_cast<const uint32_t*>(sh->ft_bits),
+        KNN_HIP(launch_renumber_labels(m->per[s].lmap, sh->ntotal,
+                                       reinterpret_cast<const uint32_t*>(sh->ft_bits.get()),
                                        sh->rm_pref, nbits, removed, ss));
         KNN_HIP(hipStreamSynchronize(ss));
         if ((rc = fence_end_synced(sh)) != KNN_OK) return rc;
@@ -342,8 +319,8 @@ int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, i
     int rc;
     {
         DeviceGuard g(ix->device);
-        if ((rc = grow(&m->gD, &m->gD_cap, nk * ndev)) != KNN_OK) return rc;
-        if ((rc = grow(&m->gI, &m->gI_cap, nk * ndev)) != KNN_OK) return rc;
+        if ((rc = m->gD.reserve(nk * ndev)) != KNN_OK) return rc;
+        if ((rc = m->gI.reserve(nk * ndev)) != KNN_OK) return rc;
         KNN_HIP(hipEventRecord(m->ready, st));
     }
     for (int s = 0; s < ndev; ++s) {
@@ -358,29 +335,29 @@ int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, i
         float* ds = m->gD + s * nk;
         int64_t* is = m->gI + s * nk;
         if (!local) {
-            if ((rc = grow(&m->sq[s], &m->sq_cap[s], (size_t)nq * ix->d)) != KNN_OK) return rc;
-            if ((rc = grow(&m->sd[s], &m->sd_cap[s], nk)) != KNN_OK) return rc;
-            if ((rc = grow(&m->si[s], &m->si_cap[s], nk)) != KNN_OK) return rc;
-            KNN_HIP(hipMemcpyPeerAsync(m->sq[s], sh->device, q, ix->device,
+            if ((rc = m->per[s].sq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
+            if ((rc = m->per[s].sd.reserve(nk)) != KNN_OK) return rc;
+            if ((rc = m->per[s].si.reserve(nk)) != KNN_OK) return rc;
+            KNN_HIP(hipMemcpyPeerAsync(m->per[s].sq, sh->device, q, ix->device,
                                        (size_t)nq * ix->d * sizeof(float), ss));
-            qs = m->sq[s];
-            ds = m->sd[s];
-            is = m->si[s];
+            qs = m->per[s].sq;
+            ds = m->per[s].sd;
+            is = m->per[s].si;
         }
         if (filtered) {
             const uint8_t* bs = bits;
             const size_t nbytes = (size_t)((nbits + 7) / 8);
             if (!local && nbytes) {
-                if ((rc = grow(&m->sb[s], &m->sb_cap[s], nbytes)) != KNN_OK) return rc;
-                KNN_HIP(hipMemcpyPeerAsync(m->sb[s], sh->device, bits, ix->device, nbytes, ss));
-                bs = m->sb[s];
+                if ((rc = m->per[s].sb.reserve(nbytes)) != KNN_OK) return rc;
+                KNN_HIP(hipMemcpyPeerAsync(m->per[s].sb, sh->device, bits, ix->device, nbytes, ss));
+                bs = m->per[s].sb;
             }
-            rc = filtered_search_locked(sh, qs, nq, k, bs, nbits, m->lmap[s], ds, is, ss);
+            rc = filtered_search_locked(sh, qs, nq, k, bs, nbits, m->per[s].lmap, ds, is, ss);
         } else {
             rc = search_locked(sh, qs, nq, k, ds, is, ss);
         }
         if (rc != KNN_OK) return rc;
-        KNN_HIP(launch_map_labels(is, (int64_t)nk, m->lmap[s], ix->id_offset, ss));
+        KNN_HIP(launch_map_labels(is, (int64_t)nk, m->per[s].lmap, ix->id_offset, ss));
         if (!local) {
             KNN_HIP(hipMemcpyPeerAsync(m->gD + s * nk, ix->device, ds, sh->device,
                                        nk * sizeof(float), ss));
@@ -388,10 +365,10 @@ int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, i
                                        nk * sizeof(int64_t), ss));
         }
         if ((rc = fence_end(sh, ss)) != KNN_OK) return rc;
-        KNN_HIP(hipEventRecord(m->done[s], ss));
+        KNN_HIP(hipEventRecord(m->per[s].done, ss));
     }
     DeviceGuard g(ix->device);
-    for (int s = 0; s < ndev; ++s) KNN_HIP(hipStreamWaitEvent(st, m->done[s], 0));
+    for (int s = 0; s < ndev; ++s) KNN_HIP(hipStreamWaitEvent(st, m->per[s].done, 0));
     const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
     if (k > KNN_MAX_K) {
         KNN_HIP(launch_merge_any(m->gD, m->gI, ndev, nq, k, (int64_t)nk, (int64_t)nk, k, kmetric, D, I, st));
@@ -423,9 +400,9 @@ int multi_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int
     DeviceGuard g(ix->device);
     int rc;
     if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)nq * ix->d)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hd, &ix->hd_cap, (size_t)nq * k)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->hi, &ix->hi_cap, (size_t)nq * k)) != KNN_OK) return rc;
+    if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
+    if ((rc = ix->hd.reserve((size_t)nq * k)) != KNN_OK) return rc;
+    if ((rc = ix->hi.reserve((size_t)nq * k)) != KNN_OK) return rc;
     KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice,
                            ix->stream));
     if (ix->ntotal == 0) {
@@ -487,7 +464,7 @@ int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq
     int rc;
     if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
     if (q_on_host && nq > 0) {
-        if ((rc = grow(&ix->hq, &ix->hq_cap, (size_t)nq * ix->d)) != KNN_OK) return rc;
+        if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
         KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
         q = ix->hq;
     }
@@ -512,10 +489,10 @@ int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq
         if ((r = fence_begin(sh, ss)) != KNN_OK) return r;
         const float* qs = q;
         if (!local && nq > 0) {
-            if ((r = grow(&m->sq[s], &m->sq_cap[s], (size_t)nq * ix->d)) != KNN_OK) return r;
-            KNN_HIP(hipMemcpyPeerAsync(m->sq[s], sh->device, q, ix->device,
+            if ((r = m->per[s].sq.reserve((size_t)nq * ix->d)) != KNN_OK) return r;
+            KNN_HIP(hipMemcpyPeerAsync(m->per[s].sq, sh->device, q, ix->device,
                                        (size_t)nq * ix->d * sizeof(float), ss));
-            qs = m->sq[s];
+            qs = m->per[s].sq;
         }
         knn_range_result* res = nullptr;
         if ((r = range_search_locked(sh, qs, nq, radius, ss, &res)) != KNN_OK) return r;
@@ -524,7 +501,7 @@ int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq
         h.D.resize((size_t)n);
         h.I.resize((size_t)n);
         hipError_t e = hipSuccess;
-        if (n > 0) e = launch_map_labels(res->I, n, m->lmap[s], ix->id_offset, ss);
+        if (n > 0) e = launch_map_labels(res->I, n, m->per[s].lmap, ix->id_offset, ss);
         if (e == hipSuccess)
             e = hipMemcpyAsync(h.lims.data(), res->lims, ((size_t)nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ss);
         if (e == hipSuccess && n > 0)

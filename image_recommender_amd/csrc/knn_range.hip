@@ -253,37 +253,35 @@ int new_result(int device, int64_t nq, knn_range_result** out) {
     r->nq = nq;
     *out = r;
     KNN_HIP(hipEventCreateWithFlags(&r->done, hipEventDisableTiming));
-    KNN_HIP(hipMalloc((void**)&r->lims, (size_t)(nq + 1) * sizeof(int64_t)));
-    return KNN_OK;
+    return r->lims.reserve((size_t)(nq + 1));
 }
 
 // D / I of `n` entries (never NULL: an empty result keeps one unused element)
-int alloc_hits(int64_t n, float** D, int64_t** I) {
-    KNN_HIP(hipMalloc((void**)D, (size_t)std::max<int64_t>(n, 1) * sizeof(float)));
-    KNN_HIP(hipMalloc((void**)I, (size_t)std::max<int64_t>(n, 1) * sizeof(int64_t)));
-    return KNN_OK;
+int alloc_hits(int64_t n, DevBuf<float>& D, DevBuf<int64_t>& I) {
+    const int rc = D.reserve((size_t)std::max<int64_t>(n, 1));
+    return rc != KNN_OK ? rc : I.reserve((size_t)std::max<int64_t>(n, 1));
 }
 
-struct ChunkHits { float* D = nullptr; int64_t* I = nullptr; int64_t n = 0; };
+struct ChunkHits { DevBuf<float> D; DevBuf<int64_t> I; int64_t n = 0; };
 
 int range_chunks(knn_index* ix, const float* q, int64_t nq, float radius, hipStream_t st,
                  knn_range_result* res, std::vector<ChunkHits>& chunks) {
     const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
     const int normalize = ix->metric == KNN_METRIC_COSINE;
     int rc;
-    if (!ix->rg_total_h) KNN_HIP(hipHostMalloc((void**)&ix->rg_total_h, sizeof(unsigned long long), hipHostMallocDefault));
-    if ((rc = grow(&ix->rg_total, &ix->rg_total_cap, (size_t)1)) != KNN_OK) return rc;
+    if ((rc = ix->rg_total_h.reserve(1)) != KNN_OK) return rc;
+    if ((rc = ix->rg_total.reserve((size_t)1)) != KNN_OK) return rc;
     int64_t base = 0;
     for (int64_t c0 = 0; c0 < nq; c0 += kQueryChunk) {
         const int64_t cn = std::min(kQueryChunk, nq - c0);
         const TilePlan p = make_tile_plan(ix->ntotal, cn, ix->dp, ix->cus);
-        if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->qnorm, &ix->qnorm_cap, (size_t)p.nq_pad)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->rg_cnt, &ix->rg_cnt_cap, (size_t)cn)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->rg_off, &ix->rg_off_cap, (size_t)cn + 1)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->rg_cur, &ix->rg_cur_cap, (size_t)cn + 1)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->rg_ent, &ix->rg_ent_cap, ix->range_cap0)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->rg_entq, &ix->rg_entq_cap, ix->range_cap0)) != KNN_OK) return rc;
+        if ((rc = ix->qpad.reserve((size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
+        if ((rc = ix->qnorm.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
+        if ((rc = ix->rg_cnt.reserve((size_t)cn)) != KNN_OK) return rc;
+        if ((rc = ix->rg_off.reserve((size_t)cn + 1)) != KNN_OK) return rc;
+        if ((rc = ix->rg_cur.reserve((size_t)cn + 1)) != KNN_OK) return rc;
+        if ((rc = ix->rg_ent.reserve(ix->range_cap0)) != KNN_OK) return rc;
+        if ((rc = ix->rg_entq.reserve(ix->range_cap0)) != KNN_OK) return rc;
         KNN_HIP(launch_rows_ingest(q + c0 * ix->d, cn, ix->d, ix->dp, p.nq_pad, normalize, ix->qpad,
                                    ix->qnorm, st));
         RangeArgs a{};
@@ -294,7 +292,7 @@ int range_chunks(knn_index* ix, const float* q, int64_t nq, float radius, hipStr
         a.total = ix->rg_total; a.counts = ix->rg_cnt;
         auto pass = [&]() -> int {
             a.ent = ix->rg_ent; a.entq = ix->rg_entq;
-            a.cap = (unsigned long long)std::min(ix->rg_ent_cap, ix->rg_entq_cap);
+            a.cap = (unsigned long long)std::min(ix->rg_ent.cap(), ix->rg_entq.cap());
             KNN_HIP(hipMemsetAsync(ix->rg_total, 0, sizeof(unsigned long long), st));
             KNN_HIP(hipMemsetAsync(ix->rg_cnt, 0, (size_t)cn * sizeof(uint32_t), st));
             hipEvent_t e1 = nullptr;              // knn_set_timing: the tile kernel's own time
@@ -315,25 +313,24 @@ int range_chunks(knn_index* ix, const float* q, int64_t nq, float radius, hipStr
         if (total > (unsigned long long)UINT32_MAX)
             KNN_FAIL(KNN_EINVAL, "range search: %llu hits in one chunk of %lld queries (limit 2^32 - 1): "
                      "lower the radius or split the batch", total, (long long)cn);
-        ChunkHits h;
-        h.n = (int64_t)total;
-        chunks.push_back(h);
-        if ((rc = alloc_hits(h.n, &chunks.back().D, &chunks.back().I)) != KNN_OK) return rc;
+        chunks.emplace_back();
+        chunks.back().n = (int64_t)total;
+        if ((rc = alloc_hits((int64_t)total, chunks.back().D, chunks.back().I)) != KNN_OK) return rc;
         if (total > 0) {
             if (total > a.cap) {
                 // the counts were complete, the entries were not: the same pass with room for all
-                if ((rc = grow(&ix->rg_ent, &ix->rg_ent_cap, (size_t)total)) != KNN_OK) return rc;
-                if ((rc = grow(&ix->rg_entq, &ix->rg_entq_cap, (size_t)total)) != KNN_OK) return rc;
+                if ((rc = ix->rg_ent.reserve((size_t)total)) != KNN_OK) return rc;
+                if ((rc = ix->rg_entq.reserve((size_t)total)) != KNN_OK) return rc;
                 if ((rc = pass()) != KNN_OK) return rc;
             }
-            if ((rc = grow(&ix->rg_seg, &ix->rg_seg_cap, (size_t)total)) != KNN_OK) return rc;
+            if ((rc = ix->rg_seg.reserve((size_t)total)) != KNN_OK) return rc;
             const unsigned blocks = (unsigned)((total + 255) / 256);
             hipLaunchKernelGGL(range_scatter_kernel, dim3(blocks), dim3(256), 0, st, ix->rg_ent, ix->rg_entq,
                                (int64_t)total, ix->rg_cur, ix->rg_seg);
             KNN_HIP(hipGetLastError());
             // sorted segments land back in the append buffer (its capacity covers the total)
             KNN_HIP(sort_u64_segments(ix->rg_seg, ix->rg_ent, (int64_t)total, (int)cn, ix->rg_off, 64u,
-                                      &ix->hk_tmp, &ix->hk_tmp_cap, false, st));
+                                      ix->hk_tmp, st));
             hipLaunchKernelGGL(range_unpack_kernel, dim3(blocks), dim3(256), 0, st, ix->rg_ent, (int64_t)total,
                                kmetric, ix->id_offset, chunks.back().D, chunks.back().I);
             KNN_HIP(hipGetLastError());
@@ -341,14 +338,6 @@ int range_chunks(knn_index* ix, const float* q, int64_t nq, float radius, hipStr
         base += (int64_t)total;
     }
     return KNN_OK;
-}
-
-void free_chunks(std::vector<ChunkHits>& chunks) {
-    for (ChunkHits& c : chunks) {
-        if (c.D) (void)hipFree(c.D);
-        if (c.I) (void)hipFree(c.I);
-    }
-    chunks.clear();
 }
 
 }  // namespace
@@ -376,10 +365,10 @@ int range_search_locked(knn_index* ix, const float* q, int64_t nq, float radius,
         for (const ChunkHits& c : chunks) size += c.n;
         res->size = size;
         if (chunks.size() == 1) {
-            res->D = chunks[0].D;
-            res->I = chunks[0].I;
+            res->D = std::move(chunks[0].D);
+            res->I = std::move(chunks[0].I);
             chunks.clear();
-        } else if ((rc = alloc_hits(size, &res->D, &res->I)) == KNN_OK) {
+        } else if ((rc = alloc_hits(size, res->D, res->I)) == KNN_OK) {
             int64_t at = 0;
             for (const ChunkHits& c : chunks) {
                 if (c.n == 0) continue;
@@ -399,7 +388,7 @@ int range_search_locked(knn_index* ix, const float* q, int64_t nq, float radius,
         set_err("hipEventRecord failed");
         rc = KNN_EHIP;
     }
-    free_chunks(chunks);
+    chunks.clear();
     if (rc != KNN_OK) {
         (void)hipStreamSynchronize(st);          // nothing in flight may still write the buffers
         range_result_free(res);
@@ -415,7 +404,7 @@ int range_result_from_host(int device, int64_t nq, const int64_t* lims, const fl
     knn_range_result* res = nullptr;
     int rc = new_result(device, nq, &res);
     const int64_t size = lims[nq];
-    if (rc == KNN_OK) rc = alloc_hits(size, &res->D, &res->I);
+    if (rc == KNN_OK) rc = alloc_hits(size, res->D, res->I);
     if (rc == KNN_OK) {
         res->size = size;
         hipError_t e = hipMemcpyAsync(res->lims, lims, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st);
@@ -442,21 +431,7 @@ void range_result_free(knn_range_result* r) {
         (void)hipEventSynchronize(r->done);
         (void)hipEventDestroy(r->done);
     }
-    for (void* p : {(void*)r->lims, (void*)r->D, (void*)r->I})
-        if (p) (void)hipFree(p);
-    delete r;
-}
-
-void range_free(knn_index* ix) {
-    for (void* p : {(void*)ix->rg_ent, (void*)ix->rg_entq, (void*)ix->rg_seg, (void*)ix->rg_cnt,
-                    (void*)ix->rg_off, (void*)ix->rg_cur, (void*)ix->rg_total})
-        if (p) (void)hipFree(p);
-    if (ix->rg_total_h) (void)hipHostFree(ix->rg_total_h);
-    ix->rg_ent = ix->rg_seg = nullptr;
-    ix->rg_entq = ix->rg_cnt = ix->rg_off = ix->rg_cur = nullptr;
-    ix->rg_total = ix->rg_total_h = nullptr;
-    ix->rg_ent_cap = ix->rg_entq_cap = ix->rg_seg_cap = ix->rg_cnt_cap = ix->rg_off_cap = ix->rg_cur_cap = 0;
-    ix->rg_total_cap = 0;
+    delete r;                            // (its buffers, while the guard holds)
 }
 
 }  // namespace imgrec

@@ -117,8 +117,8 @@ int remove_rows_locked(knn_index* ix, const uint8_t* bits, int64_t nbits, const 
         KNN_FAIL(KNN_EINVAL, "remove_ids: %lld rows in one shard (limit 2^32 - 1)", (long long)ix->ntotal);
     int rc;
     // the count and the first moved row sit side by side: one copy brings both to the host
-    if ((rc = grow(&ix->ft_m, &ix->ft_m_cap, (size_t)2)) != KNN_OK) return rc;
-    if (!ix->rm_h) KNN_HIP(hipHostMalloc((void**)&ix->rm_h, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    if ((rc = ix->ft_m.reserve((size_t)2)) != KNN_OK) return rc;
+    if ((rc = ix->rm_h.reserve(2)) != KNN_OK) return rc;
     if ((rc = compact_rows(ix, bits, nbits, lmap, true, st)) != KNN_OK) return rc;
     hipLaunchKernelGGL(remove_first_kernel, dim3(1), dim3(64), 0, st, ix->ft_list, ix->ft_m);
     KNN_HIP(hipGetLastError());
@@ -128,30 +128,25 @@ int remove_rows_locked(knn_index* ix, const uint8_t* bits, int64_t nbits, const 
     if (m > old || first > m) KNN_FAIL(KNN_EHIP, "remove_ids: inconsistent survivor list");
     if (m == old) return KNN_OK;
 
+    // every live corpus column, and the caller's extra array
     struct Arr { char* p; size_t row_bytes; };
-    const Arr arrs[] = {
-        {(char*)ix->xb, (size_t)ix->dp * sizeof(float)},
-        {(char*)ix->xn, sizeof(float)},
-        {(char*)ix->xs, (size_t)ix->dp * sizeof(uint32_t)},
-        {(char*)ix->xh, (size_t)ix->dpb * sizeof(uint16_t)},
-        {(char*)ix->xr, sizeof(float)},
-        {(char*)ix->x8, (size_t)i8_row_bytes(ix->nblk8)},
-        {(char*)ix->x8s, (size_t)ix->nblk8 * sizeof(float)},
-        {(char*)ix->x8r, sizeof(float)},
-        {(char*)extra, sizeof(int64_t)},
-    };
+    Arr arrs[kCorpusColumns + 1];
+    int narr = 0;
+    Column<DeviceSpace> cols[kCorpusColumns];
+    const int ncols = corpus_columns(ix, cols);
+    for (int i = 0; i < ncols; ++i) arrs[narr++] = {(char*)cols[i].buf->data(), cols[i].stride};
+    if (extra) arrs[narr++] = {(char*)extra, sizeof(int64_t)};
     size_t max_row = 0;
-    for (const Arr& a : arrs)
-        if (a.p) max_row = std::max(max_row, a.row_bytes);
+    for (int i = 0; i < narr; ++i) max_row = std::max(max_row, arrs[i].row_bytes);
     // the knob can only lower a chunk's rows: the buffer never exceeds the staging size
     size_t bounce_bytes = kBounceBytes;
     if (ix->remove_chunk > 0 && (size_t)ix->remove_chunk < kBounceBytes / max_row)
         bounce_bytes = (size_t)ix->remove_chunk * max_row;
     bounce_bytes = std::max(bounce_bytes, max_row);
     if (first < m)
-        if ((rc = grow(&ix->hq, &ix->hq_cap, (bounce_bytes + 3) / 4)) != KNN_OK) return rc;
-    for (const Arr& a : arrs) {
-        if (!a.p) continue;
+        if ((rc = ix->hq.reserve((bounce_bytes + 3) / 4)) != KNN_OK) return rc;
+    for (int i = 0; i < narr; ++i) {
+        const Arr& a = arrs[i];
         int64_t chunk = (int64_t)(bounce_bytes / a.row_bytes);
         if (ix->remove_chunk > 0) chunk = std::min(chunk, ix->remove_chunk);
         for (int64_t j0 = first; j0 < m; j0 += chunk)
@@ -170,14 +165,6 @@ hipError_t launch_renumber_labels(int64_t* lab, int64_t n, const uint32_t* words
     hipLaunchKernelGGL(renumber_labels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, lab, n,
                        words, pref, nbits, removed);
     return hipGetLastError();
-}
-
-void remove_free(knn_index* ix) {
-    if (ix->rm_h) (void)hipHostFree(ix->rm_h);
-    if (ix->rm_pref) (void)hipFree(ix->rm_pref);
-    ix->rm_h = nullptr;
-    ix->rm_pref = nullptr;
-    ix->rm_pref_cap = 0;
 }
 
 }  // namespace imgrec

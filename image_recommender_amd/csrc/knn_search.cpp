@@ -56,8 +56,8 @@ int exact_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
         // (d = 48 colour-only or d = 1968 exact mode, one query on 1M rows; profiles/r05/stream/)
         const int sp = stream_splits(ix);
         const size_t nc = (size_t)sp * KNN_MAX_K;
-        if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)nq * nc)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)nq * nc)) != KNN_OK) return rc;
+        if ((rc = ix->cand_d.reserve((size_t)nq * nc)) != KNN_OK) return rc;
+        if ((rc = ix->cand_i.reserve((size_t)nq * nc)) != KNN_OK) return rc;
         hipEvent_t e1 = nullptr;
         if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
         KNN_HIP(launch_stream_lists(ix, qpad, qnorm, nq, kmetric, sp, ix->cand_d, ix->cand_i, st));
@@ -67,8 +67,8 @@ int exact_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
         return KNN_OK;
     }
     const Plan p = make_plan(ix->ntotal, nq, k, ix->cus);
-    if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)nq * p.ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)nq * p.ncand)) != KNN_OK) return rc;
+    if ((rc = ix->cand_d.reserve((size_t)nq * p.ncand)) != KNN_OK) return rc;
+    if ((rc = ix->cand_i.reserve((size_t)nq * p.ncand)) != KNN_OK) return rc;
     TileArgs a{};
     a.wr = p.wr; a.wq = p.wq; a.km = p.km;
     a.xb = ix->xb; a.xnorm = ix->xn; a.nrows = (int)ix->ntotal; a.dp = ix->dp;
@@ -88,14 +88,14 @@ int exact_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
 int refresh_maxima(knn_index* ix, hipStream_t st) {
     if (!ix->xn_max_stale) return KNN_OK;
     int rc;
-    if ((rc = grow(&ix->xn_max, &ix->xn_max_cap, 1)) != KNN_OK) return rc;
+    if ((rc = ix->xn_max.reserve(1)) != KNN_OK) return rc;
     KNN_HIP(launch_max_norm(ix->xn, ix->ntotal, ix->xn_max, st));
     if (ix->b16_ok) {
-        if ((rc = grow(&ix->xr_max, &ix->xr_max_cap, 1)) != KNN_OK) return rc;
+        if ((rc = ix->xr_max.reserve(1)) != KNN_OK) return rc;
         KNN_HIP(launch_max_norm(ix->xr, ix->ntotal, ix->xr_max, st));
     }
     if (ix->x8) {
-        if ((rc = grow(&ix->x8r_max, &ix->x8r_max_cap, 1)) != KNN_OK) return rc;
+        if ((rc = ix->x8r_max.reserve(1)) != KNN_OK) return rc;
         KNN_HIP(launch_max_norm(ix->x8r, ix->ntotal, ix->x8r_max, st));
     }
     ix->xn_max_stale = false;
@@ -105,14 +105,14 @@ int refresh_maxima(knn_index* ix, hipStream_t st) {
 // Certificate counters (two chunk parities + per-search totals, zeroed once here; the fallback
 // prep kernel folds and re-zeroes them) and the uncertified-query list.
 int grow_stats(knn_index* ix, int64_t nq, hipStream_t st) {
+    int rc;
     if (!ix->stat) {
-        KNN_HIP(hipMalloc((void**)&ix->stat, 12 * sizeof(int)));
+        if ((rc = ix->stat.reserve(12)) != KNN_OK) return rc;
         KNN_HIP(hipMemsetAsync(ix->stat, 0, 12 * sizeof(int), st));
         ix->stat_seq = 0;
     }
-    int rc = grow(&ix->fail, &ix->fail_cap, (size_t)nq);
-    if (rc != KNN_OK) return rc;
-    return grow(&ix->chance, &ix->chance_cap, (size_t)nq);
+    if ((rc = ix->fail.reserve((size_t)nq)) != KNN_OK) return rc;
+    return ix->chance.reserve((size_t)nq);
 }
 
 // The rerank + certificate of a candidate chunk, then its whole tail in ONE launch
@@ -133,11 +133,11 @@ int certify_chunk(knn_index* ix, RerankArgs& r, const float* qpad, const float* 
     // lists need cap_rows x lists_km (sizing by the grid alone overflowed there)
     const size_t ncap = (size_t)std::max<int64_t>(grid, cap_rows / 32) * 32 * lists_km;
     int rc;
-    if ((rc = grow(&ix->fb_q, &ix->fb_q_cap, (size_t)cap_rows * ix->dp)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->fb_qn, &ix->fb_qn_cap, (size_t)cap_rows)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->fb_cd, &ix->fb_cd_cap, ncap)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->fb_ci, &ix->fb_ci_cap, ncap)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->tail_ctl, &ix->tail_ctl_cap, (size_t)4 + cap_rows / 32)) != KNN_OK) return rc;
+    if ((rc = ix->fb_q.reserve((size_t)cap_rows * ix->dp)) != KNN_OK) return rc;
+    if ((rc = ix->fb_qn.reserve((size_t)cap_rows)) != KNN_OK) return rc;
+    if ((rc = ix->fb_cd.reserve(ncap)) != KNN_OK) return rc;
+    if ((rc = ix->fb_ci.reserve(ncap)) != KNN_OK) return rc;
+    if ((rc = ix->tail_ctl.reserve((size_t)4 + cap_rows / 32)) != KNN_OK) return rc;
     r.stats = ix->stat + 4 * parity;
     r.fail_list = ix->fail;
     r.chance_list = ix->chance;
@@ -152,13 +152,13 @@ int certify_chunk(knn_index* ix, RerankArgs& r, const float* qpad, const float* 
         // S k <= 1024 = kWideCap, knn_certify.h: it stages the S lists of k in LDS)
         r.sc_slices = std::max(1, std::min({kSlices, 64, r.raw_lists, 1024 / k}));
         const size_t ns = (size_t)nq * r.sc_slices * k;
-        if ((rc = grow(&ix->sc_key, &ix->sc_key_cap, ns)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->sc_lab, &ix->sc_lab_cap, ns)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->sc_meta, &ix->sc_meta_cap, (size_t)nq * r.sc_slices * 4)) != KNN_OK) return rc;
-        const size_t c0 = ix->sc_done_cap;
-        if ((rc = grow(&ix->sc_done, &ix->sc_done_cap, (size_t)nq)) != KNN_OK) return rc;
-        if (ix->sc_done_cap != c0)      // (re)allocated: the self-resetting counters start at 0
-            KNN_HIP(hipMemsetAsync(ix->sc_done, 0, ix->sc_done_cap * sizeof(int), st));
+        if ((rc = ix->sc_key.reserve(ns)) != KNN_OK) return rc;
+        if ((rc = ix->sc_lab.reserve(ns)) != KNN_OK) return rc;
+        if ((rc = ix->sc_meta.reserve((size_t)nq * r.sc_slices * 4)) != KNN_OK) return rc;
+        const size_t c0 = ix->sc_done.cap();
+        if ((rc = ix->sc_done.reserve((size_t)nq)) != KNN_OK) return rc;
+        if (ix->sc_done.cap() != c0)      // (re)allocated: the self-resetting counters start at 0
+            KNN_HIP(hipMemsetAsync(ix->sc_done, 0, ix->sc_done.cap() * sizeof(int), st));
         r.sc_key = ix->sc_key; r.sc_lab = ix->sc_lab; r.sc_meta = ix->sc_meta; r.sc_done = ix->sc_done;
     }
     r.tail_ctl = ix->tail_ctl;
@@ -238,11 +238,11 @@ bool fuse_merge_single(const knn_index* ix, int nlists, int km) {
 // and, for the chains that merge with launch_merge_candidates, the merge floor.
 int grow_cand(knn_index* ix, int64_t nq, int ncand, int kc, bool floor) {
     int rc;
-    if ((rc = grow(&ix->cand_d, &ix->cand_d_cap, (size_t)nq * ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand_i, &ix->cand_i_cap, (size_t)nq * ncand)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand2_d, &ix->cand2_d_cap, (size_t)nq * kc)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->cand2_i, &ix->cand2_i_cap, (size_t)nq * kc)) != KNN_OK) return rc;
-    return floor ? grow(&ix->floor, &ix->floor_cap, (size_t)nq) : KNN_OK;
+    if ((rc = ix->cand_d.reserve((size_t)nq * ncand)) != KNN_OK) return rc;
+    if ((rc = ix->cand_i.reserve((size_t)nq * ncand)) != KNN_OK) return rc;
+    if ((rc = ix->cand2_d.reserve((size_t)nq * kc)) != KNN_OK) return rc;
+    if ((rc = ix->cand2_i.reserve((size_t)nq * kc)) != KNN_OK) return rc;
+    return floor ? ix->floor.reserve((size_t)nq) : KNN_OK;
 }
 
 // The RerankArgs fields every candidate chain sets alike.  The caller adds its arithmetic's bound
@@ -266,9 +266,9 @@ int merge_for_rerank(knn_index* ix, int64_t nq, int nlists, int km, int ncand, b
     const int kc = r->kc, ngrp = (nlists + 63) / 64;
     int rc;
     if (ngrp > 1) {
-        if ((rc = grow(&ix->mws_d, &ix->mws_d_cap, (size_t)nq * ngrp * kc)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->mws_i, &ix->mws_i_cap, (size_t)nq * ngrp * kc)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->mws_f, &ix->mws_f_cap, (size_t)nq * ngrp)) != KNN_OK) return rc;
+        if ((rc = ix->mws_d.reserve((size_t)nq * ngrp * kc)) != KNN_OK) return rc;
+        if ((rc = ix->mws_i.reserve((size_t)nq * ngrp * kc)) != KNN_OK) return rc;
+        if ((rc = ix->mws_f.reserve((size_t)nq * ngrp)) != KNN_OK) return rc;
     }
     int l1G = 0;
     const bool l0 = !single && fuse_merge_level1(ix, nq, nlists, km);
@@ -295,7 +295,7 @@ int shared_bound_prep(knn_index* ix, const Plan& p, const float* qnorm, hipStrea
     if (!ix->shared_bound || !p.big) return KNN_OK;
     int rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->sbound, &ix->sbound_cap, (size_t)p.nq_pad * kSBWords)) != KNN_OK) return rc;
+    if ((rc = ix->sbound.reserve((size_t)p.nq_pad * kSBWords)) != KNN_OK) return rc;
     sb->rec = ix->sbound;
     sb->qnorm = qnorm;
     sb->xn_max = ix->xn_max;
@@ -317,8 +317,8 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     const int km = p.km;
     int rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->qb16, &ix->qb16_cap, (size_t)p.nq_pad * ix->dpb)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->q_resid, &ix->q_resid_cap, (size_t)p.nq_pad)) != KNN_OK) return rc;
+    if ((rc = ix->qb16.reserve((size_t)p.nq_pad * ix->dpb)) != KNN_OK) return rc;
+    if ((rc = ix->q_resid.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
     if ((rc = grow_cand(ix, nq, p.ncand, kc, true)) != KNN_OK) return rc;
     if ((rc = grow_stats(ix, nq, st)) != KNN_OK) return rc;
     // (the prep — here or search_locked's — also resets the shared screen bound's records)
@@ -328,8 +328,8 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
         KNN_HIP(launch_bf16_rows(qpad, p.nq_pad, ix->dp, ix->dpb, ix->qb16, ix->q_resid, st, &sb));
     TileArgs a{};
     a.wr = p.wr; a.wq = p.wq; a.km = km; a.wb = kB16WB; a.mode = kModeBF16;
-    a.xb = reinterpret_cast<const float*>(ix->xh); a.xnorm = ix->xn; a.nrows = (int)ix->ntotal;
-    a.dp = ix->dpb / 2; a.qp = reinterpret_cast<const float*>(ix->qb16); a.qnorm = qnorm;
+    a.xb = reinterpret_cast<const float*>(ix->xh.get()); a.xnorm = ix->xn; a.nrows = (int)ix->ntotal;
+    a.dp = ix->dpb / 2; a.qp = reinterpret_cast<const float*>(ix->qb16.get()); a.qnorm = qnorm;
     a.nq = (int)nq; a.metric = kmetric; a.ntiles = p.ntiles; a.nsplit = p.nsplit; a.nqb = p.nqb;
     a.id_offset = ix->id_offset; a.cand_d = ix->cand_d; a.cand_i = ix->cand_i; a.ncand = p.ncand;
     a.ib = p.big ? p.ib : 0;
@@ -395,7 +395,7 @@ int i8_chunk(knn_index* ix, const float* qraw, const float* qpad, const float* q
         (ix->i8_pool_forced || (nq == 1 && p.nsplit == ix->cus))) {
         // run-time pool of the last row groups (I8Args::pool): replaces the half_k shift
         if (!ix->i8_dyn) {
-            KNN_HIP(hipMalloc((void**)&ix->i8_dyn, 2 * sizeof(int)));
+            if ((rc = ix->i8_dyn.reserve(2)) != KNN_OK) return rc;
             KNN_HIP(hipMemsetAsync(ix->i8_dyn, 0, 2 * sizeof(int), st));
         }
         a.dyn = ix->i8_dyn;
@@ -404,10 +404,10 @@ int i8_chunk(knn_index* ix, const float* qraw, const float* qpad, const float* q
         a.half_k = 0;
     }
     if (direct) {
-        if ((rc = grow(&ix->tail_ctl, &ix->tail_ctl_cap, (size_t)4 + round_up(nq, 32) / 32)) != KNN_OK)
+        if ((rc = ix->tail_ctl.reserve((size_t)4 + round_up(nq, 32) / 32)) != KNN_OK)
             return rc;
         a.zero_ctl = ix->tail_ctl;
-        if ((rc = grow(&ix->heads, &ix->heads_cap, (size_t)nq * p.nsplit)) != KNN_OK) return rc;
+        if ((rc = ix->heads.reserve((size_t)nq * p.nsplit)) != KNN_OK) return rc;
         a.heads = ix->heads;
     }
     hipEvent_t e1 = nullptr;
@@ -440,14 +440,14 @@ int split_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
     int rc;
     if ((rc = ensure_split(ix, st)) != KNN_OK) return rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
-    if ((rc = grow(&ix->qsplit, &ix->qsplit_cap, (size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
+    if ((rc = ix->qsplit.reserve((size_t)p.nq_pad * ix->dp)) != KNN_OK) return rc;
     if ((rc = grow_cand(ix, nq, p.ncand, kc, false)) != KNN_OK) return rc;   // (launch_merge: no floor)
     if ((rc = grow_stats(ix, nq, st)) != KNN_OK) return rc;
     KNN_HIP(launch_split_rows(qpad, p.nq_pad, ix->dp, kSplitBK, ix->qsplit, st));
     TileArgs a{};
     a.wr = p.wr; a.wq = p.wq; a.km = kc;
-    a.xb = reinterpret_cast<const float*>(ix->xs); a.xnorm = ix->xn; a.nrows = (int)ix->ntotal;
-    a.dp = ix->dp; a.qp = reinterpret_cast<const float*>(ix->qsplit); a.qnorm = qnorm;
+    a.xb = reinterpret_cast<const float*>(ix->xs.get()); a.xnorm = ix->xn; a.nrows = (int)ix->ntotal;
+    a.dp = ix->dp; a.qp = reinterpret_cast<const float*>(ix->qsplit.get()); a.qnorm = qnorm;
     a.nq = (int)nq; a.metric = kmetric; a.ntiles = p.ntiles; a.nsplit = p.nsplit; a.nqb = p.nqb;
     a.id_offset = ix->id_offset; a.cand_d = ix->cand_d; a.cand_i = ix->cand_i;
     a.ncand = p.ncand; a.mode = kModeSplit;
@@ -547,8 +547,8 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
         const int64_t nq_pad = p.nq_pad;
         int rc;
         if (c0 == 0) ix->last_path = i8 ? 3 : (b16 ? 2 : (split ? 1 : 0));
-        if ((rc = grow(&ix->qpad, &ix->qpad_cap, (size_t)nq_pad * ix->dp)) != KNN_OK) return rc;
-        if ((rc = grow(&ix->qnorm, &ix->qnorm_cap, (size_t)nq_pad)) != KNN_OK) return rc;
+        if ((rc = ix->qpad.reserve((size_t)nq_pad * ix->dp)) != KNN_OK) return rc;
+        if ((rc = ix->qnorm.reserve((size_t)nq_pad)) != KNN_OK) return rc;
         bool q_ready = false;
         // fused query prep: fp32 padded rows + norms + bf16 + residuals, or for the int8 path
         // the same rows and norms + the two-level int8 codes (one short pass instead of
@@ -556,19 +556,19 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
         // (the int8 path's prep runs inside its scan unless IMGREC_I8_FUSED_PREP=0: nq_pad = cn)
         const bool i8_fused = i8 && ix->i8_fused_prep && nq_pad == cn && cn <= 4;
         if (i8) {
-            if ((rc = grow(&ix->q8r, &ix->q8r_cap, (size_t)cn)) != KNN_OK) return rc;
+            if ((rc = ix->q8r.reserve((size_t)cn)) != KNN_OK) return rc;
         }
         if (i8_fused) {
             q_ready = true;
         } else if (i8) {
-            if ((rc = grow(&ix->q8, &ix->q8_cap, (size_t)cn * ix->nblk8 * 128)) != KNN_OK) return rc;
-            if ((rc = grow(&ix->q8s, &ix->q8s_cap, (size_t)cn * ix->nblk8 * 2)) != KNN_OK) return rc;
+            if ((rc = ix->q8.reserve((size_t)cn * ix->nblk8 * 128)) != KNN_OK) return rc;
+            if ((rc = ix->q8s.reserve((size_t)cn * ix->nblk8 * 2)) != KNN_OK) return rc;
             KNN_HIP(launch_i8_query_prep(q + c0 * ix->d, cn, ix->d, ix->dp, nq_pad, normalize,
                                          ix->nblk8, ix->qpad, ix->qnorm, ix->q8, ix->q8s, ix->q8r, st));
             q_ready = true;
         } else if (b16 && ix->dpb <= 4096) {
-            if ((rc = grow(&ix->qb16, &ix->qb16_cap, (size_t)nq_pad * ix->dpb)) != KNN_OK) return rc;
-            if ((rc = grow(&ix->q_resid, &ix->q_resid_cap, (size_t)nq_pad)) != KNN_OK) return rc;
+            if ((rc = ix->qb16.reserve((size_t)nq_pad * ix->dpb)) != KNN_OK) return rc;
+            if ((rc = ix->q_resid.reserve((size_t)nq_pad)) != KNN_OK) return rc;
             SharedBoundPrep sb;
             if ((rc = shared_bound_prep(ix, p, ix->qnorm, st, &sb)) != KNN_OK) return rc;
             KNN_HIP(launch_query_prep_b16(q + c0 * ix->d, cn, ix->d, ix->dp, ix->dpb, nq_pad,

@@ -12,8 +12,9 @@ reference runs per image:
             bf16 GEMMs from weights cast once, fp32 LayerNorm / residual stream, the fused HIP
             passes of include/imgrec_vit.h; RANDOM weights (the pretrained weights cannot be
             downloaded here: throughput only)
-  index     concatenate [colour 48 | dreamsim 1792] = 1840-d rows (the SIFT part needs the
-            reference's trained VLAD codebook, which is not in the repo) and add them to the
+  index     concatenate [colour 48 | dreamsim 1792] = 1840-d rows (no SIFT part: the codebook
+            (faiss_compat.Kmeans) and the VLAD step (vlad.SoftVLAD) exist, SIFT detection and
+            the reference's MLP encoder do not) and add them to the
             resident exact index (HBM copy, norms, bf16 copy)
   search    1024 queries (normalised concatenations of the first 1024 images, as
             main/search_from_image.py:305-322 builds them), k = 10

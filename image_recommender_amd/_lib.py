@@ -24,6 +24,9 @@ COLOR_HIST_MAX_BINS = 32
 INGEST_NOT_FAST, INGEST_TOO_SMALL = -1, -2
 KMEANS_SPHERICAL = 1          # include/imgrec_kmeans.h
 KMEANS_STATS_PER_ITER = 8
+VLAD_RAW = 1                  # include/imgrec_vlad.h
+VLAD_MAX_NN = 8
+VLAD_MAX_D = 16384
 
 
 class KmeansParams(C.Structure):
@@ -93,6 +96,9 @@ SIGNATURES = {
     "kmeans_split_device": (_i, [_vp, _i, _i, _vp, _pi, _vp]),
     "kmeans_train": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _pd, _vp]),
     "kmeans_train_device": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _pd, _vp, _vp]),
+    # imgrec_vlad.h
+    "vlad_encode_device": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    "vlad_encode": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _i]),
     # imgrec_color.h
     "color_hist_device": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "color_hist_host": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _vp]),

@@ -1,23 +1,13 @@
 // knn_kmeans.hip — Lloyd k-means (faiss Clustering::train; include/imgrec_kmeans.h).
 //
 // One step (kmeans_step_device) is six launches on the caller's stream, none of which waits:
-//   1. kmeans_norms_kernel      |c|^2 of the k centroids (one wave per row, fixed order).
-//   2. kmeans_assign_kernel     a workgroup of 8 waves owns kBM = 128 points and streams the
-//                               centroids in tiles of kBN = 256 through LDS, kBK = 32 columns (one
-//                               128-byte line of every row) per stage.  One stage buffer: the next
-//                               stage's global loads are issued before the MFMAs, wait in registers
-//                               and are stored between two barriers.  Four waves split a tile's
-//                               centroids (64 each), two the points (64 each): a wave holds 2 x 2
-//                               accumulators of v_mfma_f32_32x32x2_f32 with the centroids as A (rows)
-//                               and the points as B (columns), so a lane owns one point per column
-//                               block and its 16 accumulator registers are 16 centroids of that
-//                               point: the running (key, id) minimum needs no cross-lane step until
-//                               the end.  With k <= 256 every point row is loaded once; with more
-//                               tiles the workgroup's 128 rows are re-read once per tile (from L2).
-//                               Then the waves' minima meet in LDS, the distance to the chosen
-//                               centroid is summed directly (four points at a time per wave), and
-//                               the workgroup's 128 distances are added in float64 in point order
-//                               into partial[block].
+//   1. kmeans_norms_kernel      |c|^2 of the k centroids (rows_tile.h row_norms).
+//   2. kmeans_assign_kernel     the row tile of rows_tile.h with the centroids as the rows: a lane
+//                               keeps a running (key, id) minimum per point over the stream's keys,
+//                               fmaf(-2, x.c, |c|^2) or -x.c.  Then the waves' minima meet in LDS,
+//                               the distance to the chosen centroid is summed directly (four points
+//                               at a time per wave), and the workgroup's 128 distances are added in
+//                               float64 in point order into partial[block].
 //   3. kmeans_obj_kernel        the partials, strided over 256 threads and then in thread order.
 //   4. rocPRIM radix_sort_pairs (assign, point index) on ceil(log2 k) key bits: stable, so a
 //                               cluster's members are in ascending point index.
@@ -27,18 +17,12 @@
 //                               read coalesced), members added in order; kmeans_combine_kernel adds
 //                               a cluster's part sums in part order and divides.
 //
-// Determinism.  A key is an fmaf chain over the depth in one order for every (centroid, point)
-// pair: which tile, wave, lane or register a centroid falls in changes nothing, so two bitwise-equal
-// centroid rows give bitwise-equal keys and the smaller id wins.  Zero padding of the depth adds
-// +0 products to every pair alike.  The (key, id) comparison is lexicographic at every level.
+// Determinism.  Keys: rows_tile.h's argument, so two bitwise-equal centroid rows give bitwise-equal
+// keys and the smaller id wins: the (key, id) comparison is lexicographic at every level.
 // The update's summation tree depends on P alone: not on the grid, not on dispatch order.
 //
-// LDS: 384 rows x 36 floats (32 + 4 pad: the 16 rows a quarter wave reads as float4 fall in
-// distinct banks) = 55,296 B plus 256 norms: 55 KB; the waves' minima and the workgroup's results
-// reuse the stage buffer after the last stage.  188 VGPRs: two waves per SIMD, one workgroup per CU.
-// (A 64-point, 16-column, double-buffered form of this kernel ran 49 / 67 TF where this one runs
-// 57 / 80 TF at d = 128, k = 256 / d = 768, k = 1024: it fetched half a line per row and stage and
-// re-read the centroids twice as often; profiles/kmeans/.)
+// kmeans_assign_kernel: the tile's 55 KB of LDS (the waves' minima and the workgroup's results reuse
+// the stage buffer after the stream), 184 VGPRs: two waves per SIMD, one workgroup per CU.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,7 +33,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <map>
 #include <random>
 #include <unordered_set>
 
@@ -57,58 +40,22 @@
 #include <rocprim/iterator/counting_iterator.hpp>
 
 #include "../../include/imgrec_kmeans.h"
-#include "knn_index.h"
+#include "dev_workspace.h"
+#include "rows_tile.h"
 
 namespace imgrec {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBM = 128;                // points per workgroup
-constexpr int kBN = 256;                // centroids per tile
-constexpr int kBK = 32;                 // depth per stage: a row's 128-byte line
-constexpr int kLDK = kBK + 4;           // LDS row stride (floats)
-constexpr int kNT = 512;                // threads: 4 waves over the centroids x 2 over the points
-constexpr int kQ = kBK / 4;             // float4 per row and stage
-constexpr int kRows = kBN + kBM;        // rows per stage: the centroid tile, then the points
-constexpr int kLd4 = kRows * kQ / kNT;  // float4 loads per thread and stage
 constexpr int kPartDefault = 256;       // members per part of the segmented sum
 constexpr float kSplitEps = 1.0f / 1024.0f;
-static_assert(kRows * kQ % kNT == 0 && kBM == 2 * 64 && kBN == 4 * 64, "stage loads divide evenly");
-
-// columns [col, col + 4) of row `row` (zeros outside the matrix)
-__device__ __forceinline__ float4 load_row4(const float* __restrict__ base, int64_t row, int64_t nrows,
-                                            int d, int col, bool vec) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < nrows && col < d) {
-        const float* p = base + row * (int64_t)d + col;
-        if (vec && col + 4 <= d) {
-            v = *reinterpret_cast<const float4*>(p);
-        } else {
-            v.x = p[0];
-            if (col + 1 < d) v.y = p[1];
-            if (col + 2 < d) v.z = p[2];
-            if (col + 3 < d) v.w = p[3];
-        }
-    }
-    return v;
-}
 
 __device__ __forceinline__ void take_min(float& bk, int& bi, float k, int i) {
-    if (k < bk || (k == bk && i < bi)) { bk = k; bi = i; }
+    if (key_less(k, i, bk, bi)) { bk = k; bi = i; }
 }
 
-// out[r] = |row r|^2, one wave per row: lanes stride the columns, then a fixed butterfly
 __global__ void __launch_bounds__(256)
 kmeans_norms_kernel(const float* __restrict__ c, int k, int d, float* __restrict__ out) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= k) return;
-    const float* p = c + (int64_t)row * d;
-    float s = 0.f;
-    for (int j = lane; j < d; j += 64) s = fmaf(p[j], p[j], s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) out[row] = s;
+    row_norms(c, k, d, out);
 }
 
 __global__ void __launch_bounds__(kNT)
@@ -124,99 +71,15 @@ kmeans_assign_kernel(const float* __restrict__ x, int64_t n, int d, const float*
     float* const s_d = stage + 9 * kBM;                                // [kBM]
     static_assert(10 * kBM <= kRows * kLDK, "results fit the stage buffer");
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
-    const int wc = wave & 3, wp = wave >> 2;     // the wave's 64 centroids of the tile, its 64 points
+    const RowLanes t;
+    const int tid = t.tid, lane = t.lane, wave = t.wave, lr = t.lr, lh = t.lh, wc = t.wc, wp = t.wp;
     const int64_t p0 = (int64_t)blockIdx.x * kBM;
-    const int nkc = (d + kBK - 1) / kBK, nct = (k + kBN - 1) / kBN;
-    const int total = nct * nkc;            // < 2^31: checked on the host
-
-    float4 pre[kLd4];
-    auto fetch = [&](int s) __attribute__((always_inline)) {
-        const int ct = s / nkc, kc = s - ct * nkc;
-#pragma unroll
-        for (int it = 0; it < kLd4; ++it) {
-            const int idx = tid + it * kNT, row = idx / kQ, col = kc * kBK + 4 * (idx % kQ);
-            pre[it] = row < kBN ? load_row4(c, (int64_t)ct * kBN + row, k, d, col, vec_c)
-                                : load_row4(x, p0 + (row - kBN), n, d, col, vec_x);
-        }
-    };
-    auto store = [&](int s) __attribute__((always_inline)) {
-#pragma unroll
-        for (int it = 0; it < kLd4; ++it) {
-            const int idx = tid + it * kNT;
-            *reinterpret_cast<float4*>(stage + (idx / kQ) * kLDK + 4 * (idx % kQ)) = pre[it];
-        }
-        const int ct = s / nkc;
-        if (s - ct * nkc == 0 && tid < kBN) {    // a tile's first stage brings its norms
-            const int64_t cid = (int64_t)ct * kBN + tid;
-            cns[tid] = cid < k ? cn[cid] : 0.f;
-        }
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
     float bk[2] = {INFINITY, INFINITY};
     int bi[2] = {INT32_MAX, INT32_MAX};
-
-    fetch(0);
-    store(0);
-    __syncthreads();
-    for (int s = 0; s < total; ++s) {
-        if (s + 1 < total) fetch(s + 1);     // in flight during the MFMAs
-        // a half wave takes columns 8 g + 4 lh .. + 3 of each group g of 8: the depth order is a
-        // permutation of the columns, the same for every pair
-#pragma unroll
-        for (int g = 0; g < kBK / 8; ++g) {
-            float av[2][4], bv[2][4];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const float4 v = *reinterpret_cast<const float4*>(
-                    stage + (wc * 64 + a * 32 + lr) * kLDK + 8 * g + 4 * lh);
-                av[a][0] = v.x; av[a][1] = v.y; av[a][2] = v.z; av[a][3] = v.w;
-            }
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const float4 v = *reinterpret_cast<const float4*>(
-                    stage + (kBN + wp * 64 + b * 32 + lr) * kLDK + 8 * g + 4 * lh);
-                bv[b][0] = v.x; bv[b][1] = v.y; bv[b][2] = v.z; bv[b][3] = v.w;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][e], bv[b][e], acc[a][b], 0, 0, 0);
-        }
-        const int ct = s / nkc;
-        if (s - ct * nkc == nkc - 1) {       // the tile's last stage: keys, running minimum
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int i = wc * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const int64_t cid = (int64_t)ct * kBN + i;
-                    if (cid < k) {
-                        const float cnv = cns[i];
-#pragma unroll
-                        for (int b = 0; b < 2; ++b) {
-                            const float key = spherical ? -acc[a][b][r] : fmaf(-2.f, acc[a][b][r], cnv);
-                            take_min(bk[b], bi[b], key, (int)cid);
-                        }
-                    }
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc[a][b][r] = 0.f;
-                }
-        }
-        __syncthreads();                     // every wave has read the stage (and the norms)
-        if (s + 1 < total) store(s + 1);
-        __syncthreads();
-    }
+    rows_stream(t, stage, cns, x, n, d, c, cn, k, vec_x, vec_c,
+                [&](int b, float dot, float cnv, int cid) __attribute__((always_inline)) {
+                    take_min(bk[b], bi[b], spherical ? -dot : fmaf(-2.f, dot, cnv), cid);
+                });
 
     // the two halves of a wave, then the four waves that share the points
 #pragma unroll
@@ -429,14 +292,8 @@ kmeans_gather_kernel(const float* __restrict__ src, int d, const int64_t* __rest
 
 // ---- host side ----------------------------------------------------------------------------------
 
-// One workspace per device, shared by every call on it: calls hold `mu` while they enqueue, and a
-// call on another stream than the previous one first waits for that call's event.  It lives as
-// long as the process (never deleted: its buffers go with the process).
-struct Workspace {
-    std::mutex mu;
-    hipEvent_t done = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
+// what a step's launches share (dev_workspace.h: one per device)
+struct Workspace : StreamHandoff {
     DevBuf<float> cnorm;
     DevBuf<double> partial;
     DevBuf<uint32_t> skey;
@@ -447,27 +304,6 @@ struct Workspace {
     DevBuf<int> pairs;
     DevBuf<char> tmp;
 };
-
-Workspace* workspace(int device) {
-    static std::mutex mu;
-    static std::map<int, Workspace*> all;
-    std::lock_guard<std::mutex> lk(mu);
-    Workspace*& w = all[device];
-    if (!w) w = new Workspace();
-    return w;
-}
-
-int ws_begin(Workspace* w, hipStream_t st) {
-    if (!w->done) KNN_HIP(hipEventCreateWithFlags(&w->done, hipEventDisableTiming));
-    if (w->used && w->last != st) KNN_HIP(hipStreamWaitEvent(st, w->done, 0));
-    return KNN_OK;
-}
-int ws_end(Workspace* w, hipStream_t st) {
-    KNN_HIP(hipEventRecord(w->done, st));
-    w->last = st;
-    w->used = true;
-    return KNN_OK;
-}
 
 int check_step_args(const void* x, int64_t n, int d, const void* c, int k, const char* who) {
     if (d <= 0) KNN_FAIL(KNN_EINVAL, "%s: d must be positive (got %d)", who, d);
@@ -605,15 +441,6 @@ int check_train_args(const void* x, int64_t n, int d, int k, const kmeans_params
     return KNN_OK;
 }
 
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() {
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamDestroy(s);
-        }
-    }
-};
 struct Events {
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     ~Events() { for (hipEvent_t v : e) if (v) (void)hipEventDestroy(v); }
@@ -624,7 +451,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
     using clk = std::chrono::steady_clock;
     int device = 0;
     KNN_HIP(hipGetDevice(&device));
-    Workspace* w = workspace(device);
+    Workspace* w = per_device<Workspace>(device);
     const size_t kd = (size_t)k * d;
     DevBuf<float> ca, cb, di;
     DevBuf<int32_t> as;
@@ -651,7 +478,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
         float* nxt = cb;
         {
             std::lock_guard<std::mutex> lk(w->mu);
-            int rc = ws_begin(w, st);
+            int rc = w->begin(st);
             if (rc != KNN_OK) return rc;
             if (init) {
                 KNN_HIP(hipMemcpyAsync(cur, init, kd * sizeof(float), hipMemcpyHostToDevice, st));
@@ -676,7 +503,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
                 hipLaunchKernelGGL(kmeans_normalize_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, cur, k, d);
                 KNN_HIP(hipGetLastError());
             }
-            if ((rc = ws_end(w, st)) != KNN_OK) return rc;
+            if ((rc = w->end(st)) != KNN_OK) return rc;
         }
         const clk::time_point t0 = clk::now();
         double t_search = 0.0, obj = 0.0;
@@ -685,7 +512,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
             int nsplit = 0;
             {
                 std::lock_guard<std::mutex> lk(w->mu);
-                int rc = ws_begin(w, st);
+                int rc = w->begin(st);
                 if (rc != KNN_OK) return rc;
                 if ((rc = step_locked(w, x, n, d, cur, k, flags, as, di, nxt, cnt_d, obj_d,
                                       st, evs.e)) != KNN_OK)
@@ -704,7 +531,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
                     hipLaunchKernelGGL(kmeans_normalize_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, nxt, k, d);
                     KNN_HIP(hipGetLastError());
                 }
-                if ((rc = ws_end(w, st)) != KNN_OK) return rc;
+                if ((rc = w->end(st)) != KNN_OK) return rc;
                 float ms[3] = {0.f, 0.f, 0.f};
                 for (int e = 0; e < 3; ++e) KNN_HIP(hipEventElapsedTime(&ms[e], evs.e[e], evs.e[e + 1]));
                 double* s = &stats[(size_t)it * KMEANS_STATS_PER_ITER];
@@ -740,12 +567,6 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
     return KNN_OK;
 }
 
-int have_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) KNN_FAIL(KNN_ENOSYS, "no HIP device visible");
-    return KNN_OK;
-}
-
 }  // namespace
 }  // namespace imgrec
 
@@ -765,14 +586,14 @@ int kmeans_step_device(const float* x, int64_t n, int d, const float* centroids,
     if ((rc = have_device()) != KNN_OK) return rc;
     int device = 0;
     KNN_HIP(hipGetDevice(&device));
-    Workspace* w = workspace(device);
+    Workspace* w = per_device<Workspace>(device);
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = ws_begin(w, st)) != KNN_OK) return rc;
+    if ((rc = w->begin(st)) != KNN_OK) return rc;
     if ((rc = step_locked(w, x, n, d, centroids, k, flags, assign, dist, new_centroids, counts, obj, st,
                           nullptr)) != KNN_OK)
         return rc;
-    return ws_end(w, st);
+    return w->end(st);
 }
 
 int kmeans_split_device(float* centroids, int k, int d, int64_t* counts_host, int* nsplit, void* stream) {
@@ -791,12 +612,12 @@ int kmeans_split_device(float* centroids, int k, int d, int64_t* counts_host, in
     if ((rc = have_device()) != KNN_OK) return rc;
     int device = 0;
     KNN_HIP(hipGetDevice(&device));
-    Workspace* w = workspace(device);
+    Workspace* w = per_device<Workspace>(device);
     hipStream_t st = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = ws_begin(w, st)) != KNN_OK) return rc;
+    if ((rc = w->begin(st)) != KNN_OK) return rc;
     if ((rc = split_locked(w, centroids, k, d, counts_host, nsplit, st)) != KNN_OK) return rc;
-    return ws_end(w, st);
+    return w->end(st);
 }
 
 int kmeans_train_device(const float* x_dev, int64_t n, int d, int k, const kmeans_params_t* params,

@@ -2,21 +2,18 @@
 // _compute_sift_vlad_worker, vector_scripts/create_sift_vector.py:448-475).
 //
 // One call (vlad_encode_device) is four launches on the caller's stream, none of which waits:
-//   1. vlad_norms_kernel      |c|^2 of the k codebook rows (one wave per row, fixed order).
+//   1. vlad_norms_kernel      |c|^2 of the k codebook rows (rows_tile.h row_norms).
 //   2. vlad_nn_kernel<L>      the nn nearest rows of every descriptor, over the concatenated
-//                             descriptors (images play no part here).  The structure is that of
-//                             kmeans_assign_kernel (knn_kmeans.hip): a workgroup of 8 waves owns
-//                             128 descriptors and streams the codebook in tiles of 256 rows through
-//                             LDS, 32 columns per stage, v_mfma_f32_32x32x2_f32 with the codebook
-//                             rows as A and the descriptors as B, so a lane owns one descriptor per
-//                             column block and its 16 accumulator registers are 16 codebook rows.
-//                             Where that kernel keeps one running (key, id) minimum, a lane here
-//                             keeps a sorted list of L = 1, 2, 4 or 8 >= nn entries per descriptor
-//                             in registers (a compare against the list's tail, then an unrolled
-//                             bubble towards the head).  The two half waves' lists meet by a
-//                             cross-lane exchange, the four codebook waves' lists in LDS; one thread
-//                             per descriptor merges them.  Then |x - c|^2 of the nn listed rows is
-//                             summed directly, 16 (descriptor, row) pairs at a time per wave.
+//                             descriptors (images play no part here): the row tile of rows_tile.h
+//                             with the codebook as the rows and kmeans_assign_kernel's key,
+//                             fmaf(-2, x.c, |c|^2).  Where that kernel keeps one running (key, id)
+//                             minimum, a lane here keeps a sorted list of L = 1, 2, 4 or 8 >= nn
+//                             entries per descriptor in registers (a compare against the list's
+//                             tail, then an unrolled bubble towards the head).  The two half waves'
+//                             lists meet by a cross-lane exchange, the four codebook waves' lists in
+//                             LDS; one thread per descriptor merges them.  Then |x - c|^2 of the nn
+//                             listed rows is summed directly, 16 (descriptor, row) pairs at a time
+//                             per wave.
 //   3. vlad_aggregate_kernel  a workgroup per (image, tile of ct codebook rows); the accumulator,
 //                             ct x d sums, lives in LDS (ct = k = 256 at d = 128: 128 KiB of the
 //                             CU's 160).  A wave owns the rows with
@@ -35,15 +32,15 @@
 //                             g^2 = sum_rows (sum |v|) / r comes out of the pass that finds r.
 //                             It is a launch of its own because the norm spans the cluster tiles.
 //
-// Determinism.  Keys: knn_kmeans.hip's argument (an fmaf chain over the depth in one order for
-// every pair; lexicographic (key, id) at every level; ids are distinct, so the sorted list is
-// unique whatever the insertion order).  Aggregation: an element's members are added by its one
-// owner in ascending descriptor order, whatever ct, the grid or the image's place in the batch.
+// Determinism.  Keys: rows_tile.h's argument; lexicographic (key, id) at every level; ids are
+// distinct, so the sorted list is unique whatever the insertion order.  Aggregation: an element's
+// members are added by its one owner in ascending descriptor order, whatever ct, the grid or the
+// image's place in the batch.
 //
-// Registers and LDS.  vlad_nn_kernel: knn_kmeans.hip's stage buffer (384 rows x 36 floats, 55 KB)
-// plus 256 norms; after the last stage the buffer holds the waves' lists (4 x 128 x L keys and
-// ids) and the merged ids (128 x L): 36 KB at L = 8.  204 VGPRs (232 at L = 8) against that
-// kernel's 188: the lists, and 16 distance pairs in flight; two waves per SIMD either way.  The
+// Registers and LDS.  vlad_nn_kernel: the tile's 55 KB; after the stream the stage buffer holds the
+// waves' lists (4 x 128 x L keys and ids) and the merged ids (128 x L): 36 KB at L = 8.  204 VGPRs
+// (232 at L = 8) against kmeans_assign_kernel's 184: the lists, and 16 distance pairs in flight;
+// two waves per SIMD either way.  The
 // aggregation takes 51 VGPRs and ct x d floats of dynamic LDS.  Figures per kernel: profiles/vlad/.
 
 #include <hip/hip_runtime.h>
@@ -52,54 +49,21 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
 
 #include "../../include/imgrec_vlad.h"
-#include "knn_index.h"
+#include "dev_workspace.h"
+#include "rows_tile.h"
 #include "vlad_args.h"
 
 namespace imgrec {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBM = 128;                // descriptors per workgroup
-constexpr int kBN = 256;                // codebook rows per tile
-constexpr int kBK = 32;                 // depth per stage: a row's 128-byte line
-constexpr int kLDK = kBK + 4;           // LDS row stride (floats)
-constexpr int kNT = 512;                // threads: 4 waves over the codebook x 2 over the descriptors
-constexpr int kQ = kBK / 4;             // float4 per row and stage
-constexpr int kRows = kBN + kBM;        // rows per stage: the codebook tile, then the descriptors
-constexpr int kLd4 = kRows * kQ / kNT;  // float4 loads per thread and stage
 constexpr int kDP = 16;                 // (descriptor, row) pairs whose direct distances a wave sums at a time
 constexpr int kAG = 8;                  // list entries whose descriptor loads an aggregation wave issues together
 constexpr int kAggNT = 512;             // aggregation: 8 waves, a wave per residue of the row mod 8
 constexpr int kAggWaves = kAggNT / 64;
-static_assert(kRows * kQ % kNT == 0 && kBM == 2 * 64 && kBN == 4 * 64, "stage loads divide evenly");
 static_assert(9 * kBM * VLAD_MAX_NN <= kRows * kLDK, "the lists fit the stage buffer");
 static_assert((kAggWaves & (kAggWaves - 1)) == 0, "row ownership is a mask");
-
-// columns [col, col + 4) of row `row` (zeros outside the matrix)
-__device__ __forceinline__ float4 load_row4(const float* __restrict__ base, int64_t row, int64_t nrows,
-                                            int d, int col, bool vec) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row < nrows && col < d) {
-        const float* p = base + row * (int64_t)d + col;
-        if (vec && col + 4 <= d) {
-            v = *reinterpret_cast<const float4*>(p);
-        } else {
-            v.x = p[0];
-            if (col + 1 < d) v.y = p[1];
-            if (col + 2 < d) v.z = p[2];
-            if (col + 3 < d) v.w = p[3];
-        }
-    }
-    return v;
-}
-
-__device__ __forceinline__ bool key_less(float ka, int ia, float kb, int ib) {
-    return ka < kb || (ka == kb && ia < ib);
-}
 
 // (key, id) into a list sorted ascending: dropped unless it beats the tail
 template <int L>
@@ -120,17 +84,9 @@ __device__ __forceinline__ void list_insert(float (&lk)[L], int (&li)[L], float 
     }
 }
 
-// out[r] = |row r|^2, one wave per row: lanes stride the columns, then a fixed butterfly
 __global__ void __launch_bounds__(256)
 vlad_norms_kernel(const float* __restrict__ c, int k, int d, float* __restrict__ out) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= k) return;
-    const float* p = c + (int64_t)row * d;
-    float s = 0.f;
-    for (int j = lane; j < d; j += 64) s = fmaf(p[j], p[j], s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) out[row] = s;
+    row_norms(c, k, d, out);
 }
 
 template <int L>
@@ -145,42 +101,9 @@ vlad_nn_kernel(const float* __restrict__ x, int64_t n, int d, const float* __res
     int* const redi = reinterpret_cast<int*>(stage + 4 * kBM * L);          // [4][kBM][L]
     int* const s_id = reinterpret_cast<int*>(stage + 8 * kBM * L);          // [kBM][L]
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
-    const int wc = wave & 3, wp = wave >> 2;     // the wave's 64 rows of the tile, its 64 descriptors
+    const RowLanes t;
+    const int tid = t.tid, lane = t.lane, wave = t.wave, lr = t.lr, lh = t.lh, wc = t.wc, wp = t.wp;
     const int64_t p0 = (int64_t)blockIdx.x * kBM;
-    const int nkc = (d + kBK - 1) / kBK, nct = (k + kBN - 1) / kBN;
-    const int total = nct * nkc;            // < 2^31: checked on the host
-
-    float4 pre[kLd4];
-    auto fetch = [&](int s) __attribute__((always_inline)) {
-        const int ct = s / nkc, kc = s - ct * nkc;
-#pragma unroll
-        for (int it = 0; it < kLd4; ++it) {
-            const int idx = tid + it * kNT, row = idx / kQ, col = kc * kBK + 4 * (idx % kQ);
-            pre[it] = row < kBN ? load_row4(c, (int64_t)ct * kBN + row, k, d, col, vec_c)
-                                : load_row4(x, p0 + (row - kBN), n, d, col, vec_x);
-        }
-    };
-    auto store = [&](int s) __attribute__((always_inline)) {
-#pragma unroll
-        for (int it = 0; it < kLd4; ++it) {
-            const int idx = tid + it * kNT;
-            *reinterpret_cast<float4*>(stage + (idx / kQ) * kLDK + 4 * (idx % kQ)) = pre[it];
-        }
-        const int ct = s / nkc;
-        if (s - ct * nkc == 0 && tid < kBN) {    // a tile's first stage brings its norms
-            const int64_t cid = (int64_t)ct * kBN + tid;
-            cns[tid] = cid < k ? cn[cid] : 0.f;
-        }
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
     float lk[2][L];
     int li[2][L];
 #pragma unroll
@@ -190,59 +113,10 @@ vlad_nn_kernel(const float* __restrict__ x, int64_t n, int d, const float* __res
             lk[b][s] = INFINITY;
             li[b][s] = INT32_MAX;
         }
-
-    fetch(0);
-    store(0);
-    __syncthreads();
-    for (int s = 0; s < total; ++s) {
-        if (s + 1 < total) fetch(s + 1);     // in flight during the MFMAs
-        // a half wave takes columns 8 g + 4 lh .. + 3 of each group g of 8: the depth order is a
-        // permutation of the columns, the same for every pair
-#pragma unroll
-        for (int g = 0; g < kBK / 8; ++g) {
-            float av[2][4], bv[2][4];
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const float4 v = *reinterpret_cast<const float4*>(
-                    stage + (wc * 64 + a * 32 + lr) * kLDK + 8 * g + 4 * lh);
-                av[a][0] = v.x; av[a][1] = v.y; av[a][2] = v.z; av[a][3] = v.w;
-            }
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const float4 v = *reinterpret_cast<const float4*>(
-                    stage + (kBN + wp * 64 + b * 32 + lr) * kLDK + 8 * g + 4 * lh);
-                bv[b][0] = v.x; bv[b][1] = v.y; bv[b][2] = v.z; bv[b][3] = v.w;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][e], bv[b][e], acc[a][b], 0, 0, 0);
-        }
-        const int ct = s / nkc;
-        if (s - ct * nkc == nkc - 1) {       // the tile's last stage: keys into the lists
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int i = wc * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const int64_t cid = (int64_t)ct * kBN + i;
-                    if (cid < k) {
-                        const float cnv = cns[i];
-#pragma unroll
-                        for (int b = 0; b < 2; ++b)
-                            list_insert<L>(lk[b], li[b], fmaf(-2.f, acc[a][b][r], cnv), (int)cid);
-                    }
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) acc[a][b][r] = 0.f;
-                }
-        }
-        __syncthreads();                     // every wave has read the stage (and the norms)
-        if (s + 1 < total) store(s + 1);
-        __syncthreads();
-    }
+    rows_stream(t, stage, cns, x, n, d, c, cn, k, vec_x, vec_c,
+                [&](int b, float dot, float cnv, int cid) __attribute__((always_inline)) {
+                    list_insert<L>(lk[b], li[b], fmaf(-2.f, dot, cnv), cid);
+                });
 
     // the two halves of a wave (each takes the other's list), then the four waves that share the
     // descriptors
@@ -453,29 +327,14 @@ vlad_epilogue_kernel(float* __restrict__ out, int k, int d, double* __restrict__
 
 // ---- host side ----------------------------------------------------------------------------------
 
-// One workspace per device, shared by every call on it (knn_kmeans.hip's scheme): calls hold `mu`
-// while they enqueue, and a call on another stream than the previous one first waits for that
-// call's event.  It lives as long as the process.
-struct Workspace {
-    std::mutex mu;
-    hipEvent_t done = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
+// what a call's launches share (dev_workspace.h: one per device)
+struct Workspace : StreamHandoff {
     DevBuf<float> cnorm;
     DevBuf<int32_t> idx;
     DevBuf<float> dist;
     DevBuf<double> rnorm;
     DevBuf<double> gpart;
 };
-
-Workspace* workspace(int device) {
-    static std::mutex mu;
-    static std::map<int, Workspace*> all;
-    std::lock_guard<std::mutex> lk(mu);
-    Workspace*& w = all[device];
-    if (!w) w = new Workspace();
-    return w;
-}
 
 int check_args(const VladArgs& a, const char* who) {
     char msg[256];
@@ -551,31 +410,16 @@ int encode_device_impl(const VladArgs& a, int32_t* nn_idx, float* nn_dist, hipSt
     char msg[256];
     if (vlad_cluster_tile(a.k, a.d, acc_floats(), a.nimg, &ct, &ntiles, "vlad_encode_device", msg, sizeof msg) != 0)
         KNN_FAIL(KNN_EINVAL, "%s", msg);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) KNN_FAIL(KNN_ENOSYS, "no HIP device visible");
+    int rc = have_device();
+    if (rc != KNN_OK) return rc;
     int device = 0;
     KNN_HIP(hipGetDevice(&device));
-    Workspace* w = workspace(device);
+    Workspace* w = per_device<Workspace>(device);
     std::lock_guard<std::mutex> lk(w->mu);
-    if (!w->done) KNN_HIP(hipEventCreateWithFlags(&w->done, hipEventDisableTiming));
-    if (w->used && w->last != st) KNN_HIP(hipStreamWaitEvent(st, w->done, 0));
-    const int rc = encode_locked(w, a, ct, ntiles, nn_idx, nn_dist, st);
-    if (rc != KNN_OK) return rc;
-    KNN_HIP(hipEventRecord(w->done, st));
-    w->last = st;
-    w->used = true;
-    return KNN_OK;
+    if ((rc = w->begin(st)) != KNN_OK) return rc;
+    if ((rc = encode_locked(w, a, ct, ntiles, nn_idx, nn_dist, st)) != KNN_OK) return rc;
+    return w->end(st);
 }
-
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() {
-        if (s) {
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamDestroy(s);
-        }
-    }
-};
 
 }  // namespace
 }  // namespace imgrec
@@ -602,8 +446,9 @@ int vlad_encode(const float* x, int64_t N, const int64_t* offsets, int64_t nimg,
     char msg[256];
     if (vlad_check_offsets(offsets, nimg, N, "vlad_encode", msg, sizeof msg) != 0) KNN_FAIL(KNN_EINVAL, "%s", msg);
     if (nimg == 0) return KNN_OK;
+    if ((rc = have_device()) != KNN_OK) return rc;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) KNN_FAIL(KNN_ENOSYS, "no HIP device visible");
+    KNN_HIP(hipGetDeviceCount(&ndev));
     if (device >= ndev) KNN_FAIL(KNN_EINVAL, "vlad_encode: device %d out of range (%d visible)", device, ndev);
     DeviceGuard g(device);
     const size_t nx = (size_t)N * d, nc = (size_t)k * d, no = (size_t)nimg * k * d, nl = (size_t)N * nn;

@@ -7,7 +7,8 @@ images of 0, 1, 3, 64, 65, 300, 0 and 1000 descriptors) goes through vlad_encode
 poisoned outputs, twice, and the two runs must be byte-equal.  The float64 oracle's share of
 near-tie descriptors (checked against a margin only) is printed per case and capped at 1 % by the
 checker.  Then: batch invariance byte for byte, the optional outputs, the four ways to call, a
-cluster-tiled aggregation, from_kmeans, and agreement with IndexFlatL2.
+cluster-tiled aggregation, from_kmeans, nn = 1 byte for byte against the k-means step, and agreement
+with IndexFlatL2.
 """
 import ctypes as C
 import os
@@ -187,6 +188,30 @@ def test_from_kmeans(gpu):
     vc.check_raw(x, off, km.centroids, 125.0, idx, dist, raw)
     vc.check_final(raw, vlad, off, 32, 128)
     np.testing.assert_allclose(np.linalg.norm(vlad[np.diff(off) > 0], axis=1), 1.0, atol=1e-6)
+
+
+@pytest.mark.parametrize("n,d,k,tie", [
+    (333, 19, 300, (290, 3)),    # ragged last workgroup, scalar loads, padded depth, two codebook tiles
+    (130, 40, 7, None),          # one tile barely used, a two-row tail workgroup, a partial last stage
+])
+def test_one_neighbour_is_the_kmeans_assignment(gpu, n, d, k, tie):
+    """vlad_nn_kernel<1> and kmeans_assign_kernel run one stage stream (csrc/rows_tile.h) with one key,
+    one (key, id) order and one direct distance: nn = 1 returns, per descriptor, the bytes of
+    kmeans_step_device's assign and dist on the same rows and codebook."""
+    from tests.test_kmeans_gpu import gpu_step
+    rng = np.random.default_rng(n)
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    c = x[rng.choice(n, k, replace=False)] + 0.1 * rng.standard_normal((k, d)).astype(np.float32)
+    if tie:
+        c[tie[0]] = c[tie[1]]                        # a tie that crosses the two tiles
+    assign, dist = gpu_step(x, c)[:2]
+    _, idx, nnd = gpu_encode(x, np.array([0, n], np.int64), c, 1, 125.0, raw=True)
+    assert idx.shape == nnd.shape == (n, 1) and idx.dtype == assign.dtype and nnd.dtype == dist.dtype
+    assert np.isfinite(dist).all()
+    assert idx.tobytes() == assign.tobytes()
+    assert nnd.tobytes() == dist.tobytes()
+    if tie:
+        assert (assign == tie[1]).any() and not (assign == tie[0]).any()
 
 
 @pytest.mark.parametrize("name", ["sift", "k300", "odd19"])

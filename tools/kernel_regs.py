@@ -59,7 +59,8 @@ def main():
         if a.filter not in r["name"]:
             continue
         print(f"{r.get('VGPRs', '?'):>4} v {r.get('AGPRs', '?'):>4} a {r.get('TotalSGPRs', '?'):>4} s  spill s {r.get('SGPRs Spill', '?'):>3}"
-              f" v {r.get('VGPRs Spill', '?'):>3}  lds {r.get('LDS Size', '?'):>6}  {r['name'][:110]}")
+              f" v {r.get('VGPRs Spill', '?'):>3}  scratch {r.get('ScratchSize', '?'):>4}  waves/SIMD {r.get('Occupancy', '?'):>2}"
+              f"  lds {r.get('LDS Size', '?'):>6}  {r['name'][:110]}")
 
 
 if __name__ == "__main__":

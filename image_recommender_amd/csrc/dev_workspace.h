@@ -1,7 +1,7 @@
 // dev_workspace.h — the per-device workspace scheme of the entry points that own no index
 // (knn_kmeans.hip, vlad.hip).  One workspace per device, shared by every call on it: calls hold
 // `mu` while they enqueue, and a call on another stream than the previous one first waits for that
-// call's event.  It lives as long as the process (never deleted: its buffers go with the process).
+// call's event (HandoffOp).  It lives as long as the process (never deleted: its buffers go with the process).
 // Host code; not part of the public ABI.
 #pragma once
 
@@ -12,24 +12,16 @@
 
 namespace imgrec {
 
-// what a workspace derives from; its own members are the DevBufs its launches share
+// what a workspace derives from; its own members are the DevBufs its launches share.  The fence
+// is eager and makes its event on first use.
 struct StreamHandoff {
     std::mutex mu;
-    hipEvent_t done = nullptr;
-    hipStream_t last = nullptr;
-    bool used = false;
-    // around a call's launches on `st`, `mu` held
-    int begin(hipStream_t st) {
-        if (!done) KNN_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        if (used && last != st) KNN_HIP(hipStreamWaitEvent(st, done, 0));
-        return KNN_OK;
-    }
-    int end(hipStream_t st) {
-        KNN_HIP(hipEventRecord(done, st));
-        last = st;
-        used = true;
-        return KNN_OK;
-    }
+    Fence<HipStreams> fence;
+};
+// one call's launches on the caller's stream: begin(st) ... finish(rc) (stream_fence.h OpScope; the
+// device is the caller's current one)
+struct HandoffOp : OpScope<HipStreams> {
+    explicit HandoffOp(StreamHandoff* w) : OpScope(w->mu, -1, w->fence, nullptr) {}
 };
 
 template <class W>

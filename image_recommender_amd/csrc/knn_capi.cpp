@@ -9,8 +9,8 @@
 //
 // Stream semantics: *_device entry points enqueue on the caller's stream and return without
 // waiting for the GPU; host-pointer entry points run on the index's own stream and synchronise.
-// An operation on another stream than the previous one first waits for the previous one's stream
-// (fence_begin), so mixing streams (or host and device calls) is always ordered.
+// Every entry point that touches the GPU runs inside an IndexOp (knn_index.h; stream_fence.h), so
+// mixing streams (or host and device calls) is always ordered, also after an error exit.
 
 #include <cstdarg>
 #include <cstdio>
@@ -59,52 +59,6 @@ void set_err(const char* fmt, ...) {
 }
 
 const char* last_error() { return g_err.c_str(); }
-
-// Fences.  By default (KNN_FENCE_EAGER) an asynchronous operation records the index's fence
-// event on its stream as its last enqueued step, and the next operation on ANOTHER stream waits
-// for that event: nothing depends on the old stream afterwards (it may be destroyed, and work the
-// caller queues on it later is not waited for).  KNN_FENCE_LAZY (opt-in, knn_set_fence_mode)
-// records nothing while the stream stays the same and records the event on the remembered stream
-// only when a different stream arrives: back-to-back operations on one stream then pay no event
-// record (each costs ~5.7 us of idle GPU between the kernels around it on MI355X,
-// profiles/r03/), but the remembered stream must stay valid until that next operation, and the
-// wait covers whatever the caller queued on it meanwhile.  A lazy record that reports an error
-// falls back to a device-wide synchronisation instead of wedging the index — best effort only:
-// recording on a stream the caller has destroyed is a use after free, not a guaranteed error
-// return, so in lazy mode the stream MUST outlive the next call on the index (imgrec_knn.h).
-// Host-pointer operations synchronise their stream before returning and leave no fence.
-int fence_begin(knn_index* ix, hipStream_t st) {
-    if (!ix->fence_set || ix->fence_stream == st) return KNN_OK;
-    if (!ix->fence_recorded) {
-        if (hipEventRecord(ix->fence, ix->fence_stream) != hipSuccess) {
-            (void)hipGetLastError();
-            ix->fence_set = false;
-            KNN_HIP(hipDeviceSynchronize());
-            return KNN_OK;
-        }
-        ix->fence_recorded = true;
-    }
-    KNN_HIP(hipStreamWaitEvent(st, ix->fence, 0));
-    return KNN_OK;
-}
-
-int fence_end(knn_index* ix, hipStream_t st) {
-    ix->fence_stream = st;
-    ix->fence_set = true;
-    ix->fence_recorded = false;
-    if (!ix->fence_lazy) {
-        KNN_HIP(hipEventRecord(ix->fence, st));
-        ix->fence_recorded = true;
-    }
-    return KNN_OK;
-}
-
-// After a host-synchronous operation (its stream drained before returning): nothing to wait for.
-int fence_end_synced(knn_index* ix) {
-    ix->fence_set = false;
-    ix->fence_recorded = false;
-    return KNN_OK;
-}
 
 // The corpus column table: every per-row array of the index with its row stride in bytes.
 // reserve_rows, remove_rows_locked, add_device_locked, ensure_split and ensure_i8 all go through
@@ -285,7 +239,7 @@ int create_single(int d, int metric, int device, knn_index** out) {
         if (v > 0) ix->remove_chunk = (int64_t)v;
     }
     if (hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&ix->fence, hipEventDisableTiming) != hipSuccess) {
+        ix->fence.create() != KNN_OK) {
         if (ix->stream) (void)hipStreamDestroy(ix->stream);
         delete ix;
         KNN_FAIL(KNN_EHIP, "hipStreamCreate / hipEventCreate failed");
@@ -298,25 +252,46 @@ void free_single(knn_index* ix) {
     DeviceGuard g(ix->device);
     (void)hipDeviceSynchronize();       // searches on other streams may still use the buffers
     for (hipEvent_t e : ix->ev) (void)hipEventDestroy(e);
-    if (ix->fence) (void)hipEventDestroy(ix->fence);
     (void)hipStreamDestroy(ix->stream);
-    delete ix;                          // (every buffer, while the guard holds)
+    delete ix;                          // (every buffer and the fence's event, while the guard holds)
 }
 
-// The host form's inputs onto the index's device, on its own stream: the queries into hq, room for
-// the results in hd / hi, and the bitmap's bytes that can matter (bits at or past ntotal are
-// ignored: *nbits is lowered to ntotal) into ft_bits.
-int filtered_stage_host(knn_index* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
-                        int64_t* nbits) {
+// Batches whose query rows fit this many bytes go through page-locked staging: a pageable copy
+// is a driver-staged, host-synchronous transfer on each side of a one-query search (round 1
+// measured 47 us of PCIe-side overhead per one-query search), while a memcpy of a few KB into a
+// pinned buffer and one DMA each way are a few us.  Larger batches copy pageable memory directly.
+constexpr size_t kPinnedSearchBytes = 1 << 20;
+
+int stage_queries(knn_index* ix, const float* q, int64_t nq, int k, bool pinned) {
     int rc;
+    const size_t nqd = (size_t)nq * ix->d, nk = (size_t)nq * k;
+    if ((rc = ix->hq.reserve(nqd)) != KNN_OK) return rc;
+    if (k > 0 && (rc = ix->hd.reserve(nk)) != KNN_OK) return rc;
+    if (k > 0 && (rc = ix->hi.reserve(nk)) != KNN_OK) return rc;
+    if (pinned) {
+        if ((rc = ix->pq.reserve(nqd)) != KNN_OK) return rc;
+        if ((rc = ix->pd.reserve(nk)) != KNN_OK) return rc;
+        if ((rc = ix->pi.reserve(nk)) != KNN_OK) return rc;
+        // (the previous host-pointer search synchronised before returning: the buffers are free)
+        std::memcpy(ix->pq, q, nqd * sizeof(float));
+    }
+    KNN_HIP(hipMemcpyAsync(ix->hq, pinned ? ix->pq : q, nqd * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+    return KNN_OK;
+}
+
+int stage_bitmap(knn_index* ix, const uint8_t* bitmap, int64_t* nbits) {
     *nbits = std::min(*nbits, ix->ntotal);
     const size_t nbytes = (size_t)((*nbits + 7) / 8);
-    if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
-    if ((rc = ix->hd.reserve((size_t)nq * k)) != KNN_OK) return rc;
-    if ((rc = ix->hi.reserve((size_t)nq * k)) != KNN_OK) return rc;
-    if ((rc = ix->ft_bits.reserve(std::max<size_t>(nbytes, 1))) != KNN_OK) return rc;
-    KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+    const int rc = ix->ft_bits.reserve(std::max<size_t>(nbytes, 1));
+    if (rc != KNN_OK) return rc;
     if (nbytes) KNN_HIP(hipMemcpyAsync(ix->ft_bits, bitmap, nbytes, hipMemcpyHostToDevice, ix->stream));
+    return KNN_OK;
+}
+
+int fetch_results(knn_index* ix, int64_t nq, int k, float* D, int64_t* I) {
+    const size_t nk = (size_t)nq * k;
+    KNN_HIP(hipMemcpyAsync(D, ix->hd, nk * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    KNN_HIP(hipMemcpyAsync(I, ix->hi, nk * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
     return KNN_OK;
 }
 
@@ -382,54 +357,48 @@ int knn_train(knn_index_t* ix, const float* x, int64_t n) {
 int knn_reserve(knn_index_t* ix, int64_t n) {
     if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
     if (ix->multi) return multi_reserve(ix, n);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    int rc;
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
-    if ((rc = reserve_rows(ix, n, ix->stream)) != KNN_OK) return rc;
-    return fence_end(ix, ix->stream);
+    IndexOp op(ix);
+    int rc = op.begin(ix->stream);
+    if (rc == KNN_OK) rc = reserve_rows(ix, n, ix->stream);
+    return op.finish(rc);
+}
+
+static int add_args_ok(knn_index_t* ix, const float* x, int64_t n) {
+    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
+    if (n < 0 || (n > 0 && !x)) KNN_FAIL(KNN_EINVAL, "bad rows (n=%lld)", (long long)n);
+    return KNN_OK;
 }
 
 int knn_add_device(knn_index_t* ix, const float* x, int64_t n, void* stream) {
-    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
-    if (n < 0 || (n > 0 && !x)) KNN_FAIL(KNN_EINVAL, "bad rows (n=%lld)", (long long)n);
-    if (n == 0) return KNN_OK;
-    if (ix->multi) return multi_add_device(ix, x, n, (hipStream_t)stream);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    const hipStream_t st = (hipStream_t)stream;
     int rc;
-    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
-    if ((rc = add_device_locked(ix, x, n, st)) != KNN_OK) return rc;
-    return fence_end(ix, st);
+    if ((rc = add_args_ok(ix, x, n)) != KNN_OK || n == 0) return rc;
+    if (ix->multi) return multi_add_device(ix, x, n, (hipStream_t)stream);
+    IndexOp op(ix);
+    if ((rc = op.begin((hipStream_t)stream)) == KNN_OK) rc = add_device_locked(ix, x, n, op.stream());
+    return op.finish(rc);
 }
 
 int knn_add(knn_index_t* ix, const float* x, int64_t n) {
-    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
-    if (n < 0 || (n > 0 && !x)) KNN_FAIL(KNN_EINVAL, "bad rows (n=%lld)", (long long)n);
-    if (n == 0) return KNN_OK;
-    if (ix->multi) return multi_add(ix, x, n);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
     int rc;
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
+    if ((rc = add_args_ok(ix, x, n)) != KNN_OK || n == 0) return rc;
+    if (ix->multi) return multi_add(ix, x, n);
+    IndexOp op(ix);
+    if ((rc = op.begin_host()) != KNN_OK) return rc;
     if ((rc = reserve_rows(ix, ix->ntotal + n, ix->stream)) != KNN_OK) return rc;
     const int64_t chunk = std::max<int64_t>(1, (int64_t)(64 << 20) / ((int64_t)ix->d * 4));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t cn = std::min(chunk, n - r0);
-        if ((rc = ix->hq.reserve((size_t)cn * ix->d)) != KNN_OK) return rc;
-        KNN_HIP(hipMemcpyAsync(ix->hq, x + r0 * ix->d, (size_t)cn * ix->d * sizeof(float),
-                               hipMemcpyHostToDevice, ix->stream));
+        if ((rc = stage_queries(ix, x + r0 * ix->d, cn, 0)) != KNN_OK) return rc;
         if ((rc = add_device_locked(ix, ix->hq, cn, ix->stream)) != KNN_OK) return rc;
         KNN_HIP(hipStreamSynchronize(ix->stream));
     }
-    return fence_end_synced(ix);
+    return op.finish_synced(KNN_OK);
 }
 
 int knn_reset(knn_index_t* ix) {
     if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
     if (ix->multi) return multi_reset(ix);
-    std::lock_guard<std::mutex> lk(ix->mu);
+    IndexOp op(ix);
     ix->ntotal = 0;
     ix->xn_max_stale = true;
     return KNN_OK;
@@ -446,21 +415,13 @@ int knn_remove_ids(knn_index_t* ix, const uint8_t* bitmap, int64_t nbits, int64_
         if (rc == KNN_OK && nremoved) *nremoved = n;
         return rc;
     }
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    int rc;
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
+    IndexOp op(ix);
+    int rc = op.begin_host();
     nbits = std::min(nbits, ix->ntotal);             // bits at or past ntotal are ignored
-    if (nbits > 0) {
-        const size_t nbytes = (size_t)((nbits + 7) / 8);
-        if ((rc = ix->ft_bits.reserve(nbytes)) != KNN_OK) return rc;
-        KNN_HIP(hipMemcpyAsync(ix->ft_bits, bitmap, nbytes, hipMemcpyHostToDevice, ix->stream));
-        if ((rc = remove_rows_locked(ix, ix->ft_bits, nbits, nullptr, nullptr, ix->stream, &n)) != KNN_OK)
-            return rc;
-    }
-    KNN_HIP(hipStreamSynchronize(ix->stream));
-    if (nremoved) *nremoved = n;
-    return fence_end_synced(ix);
+    if (rc == KNN_OK && nbits > 0) rc = stage_bitmap(ix, bitmap, &nbits);
+    if (rc == KNN_OK && nbits > 0) rc = remove_rows_locked(ix, ix->ft_bits, nbits, nullptr, nullptr, ix->stream, &n);
+    if ((rc = op.finish(rc)) == KNN_OK && nremoved) *nremoved = n;
+    return rc;
 }
 
 int knn_reconstruct_n(const knn_index_t* cix, int64_t i0, int64_t n, float* x) {
@@ -471,73 +432,44 @@ int knn_reconstruct_n(const knn_index_t* cix, int64_t i0, int64_t n, float* x) {
                  (long long)(i0 + n), (long long)ix->ntotal);
     if (n == 0) return KNN_OK;
     if (ix->multi) return multi_reconstruct_n(ix, i0, n, x);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    int rc;
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
+    IndexOp op(ix);
+    if (const int rc = op.begin_host()) return rc;
     KNN_HIP(hipMemcpy2DAsync(x, (size_t)ix->d * 4, ix->xb + (size_t)i0 * ix->dp, (size_t)ix->dp * 4,
                              (size_t)ix->d * 4, (size_t)n, hipMemcpyDeviceToHost, ix->stream));
-    KNN_HIP(hipStreamSynchronize(ix->stream));
-    return fence_end_synced(ix);
+    return op.finish(KNN_OK);
+}
+
+static int search_args_ok(knn_index_t* ix, const float* q, int64_t nq, int k, const float* D, const int64_t* I) {
+    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
+    if (k <= 0) KNN_FAIL(KNN_EINVAL, "k must be >= 1 (got %d)", k);
+    if (nq < 0 || (nq > 0 && (!q || !D || !I))) KNN_FAIL(KNN_EINVAL, "bad query/output pointers");
+    return KNN_OK;
 }
 
 int knn_search_device(knn_index_t* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                       void* stream) {
-    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
-    if (k <= 0) KNN_FAIL(KNN_EINVAL, "k must be >= 1 (got %d)", k);
-    if (nq < 0 || (nq > 0 && (!q || !D || !I))) KNN_FAIL(KNN_EINVAL, "bad query/output pointers");
-    if (nq == 0) return KNN_OK;
-    if (ix->multi) return multi_search_device(ix, q, nq, k, D, I, (hipStream_t)stream);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    const hipStream_t st = (hipStream_t)stream;
     int rc;
-    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
-    if ((rc = search_locked(ix, q, nq, k, D, I, st)) != KNN_OK) return rc;
-    return fence_end(ix, st);
+    if ((rc = search_args_ok(ix, q, nq, k, D, I)) != KNN_OK || nq == 0) return rc;
+    if (ix->multi) return multi_search_device(ix, q, nq, k, D, I, (hipStream_t)stream);
+    IndexOp op(ix);
+    if ((rc = op.begin((hipStream_t)stream)) == KNN_OK) rc = search_locked(ix, q, nq, k, D, I, op.stream());
+    return op.finish(rc);
 }
 
-// Batches whose query rows fit this many bytes go through page-locked staging: a pageable copy
-// is a driver-staged, host-synchronous transfer on each side of a one-query search (round 1
-// measured 47 us of PCIe-side overhead per one-query search), while a memcpy of a few KB into a
-// pinned buffer and one DMA each way are a few us.  Larger batches copy pageable memory directly.
-constexpr size_t kPinnedSearchBytes = 1 << 20;
-
 int knn_search(knn_index_t* ix, const float* q, int64_t nq, int k, float* D, int64_t* I) {
-    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
-    if (k <= 0) KNN_FAIL(KNN_EINVAL, "k must be >= 1 (got %d)", k);
-    if (nq < 0 || (nq > 0 && (!q || !D || !I))) KNN_FAIL(KNN_EINVAL, "bad query/output pointers");
-    if (nq == 0) return KNN_OK;
-    if (ix->multi) return multi_search(ix, q, nq, k, D, I);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
     int rc;
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
-    if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
-    if ((rc = ix->hd.reserve((size_t)nq * k)) != KNN_OK) return rc;
-    if ((rc = ix->hi.reserve((size_t)nq * k)) != KNN_OK) return rc;
-    const size_t qbytes = (size_t)nq * ix->d * sizeof(float);
-    const bool pinned = qbytes <= kPinnedSearchBytes;
-    if (pinned) {
-        if ((rc = ix->pq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
-        if ((rc = ix->pd.reserve((size_t)nq * k)) != KNN_OK) return rc;
-        if ((rc = ix->pi.reserve((size_t)nq * k)) != KNN_OK) return rc;
-        // (the previous host-pointer search synchronised before returning: the buffers are free)
-        std::memcpy(ix->pq, q, qbytes);
-    }
-    KNN_HIP(hipMemcpyAsync(ix->hq, pinned ? ix->pq : q, qbytes, hipMemcpyHostToDevice, ix->stream));
-    if ((rc = search_locked(ix, ix->hq, nq, k, ix->hd, ix->hi, ix->stream)) != KNN_OK) return rc;
-    KNN_HIP(hipMemcpyAsync(pinned ? ix->pd : D, ix->hd, (size_t)nq * k * sizeof(float),
-                           hipMemcpyDeviceToHost, ix->stream));
-    KNN_HIP(hipMemcpyAsync(pinned ? ix->pi : I, ix->hi, (size_t)nq * k * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, ix->stream));
-    KNN_HIP(hipStreamSynchronize(ix->stream));
-    if ((rc = fence_end_synced(ix)) != KNN_OK) return rc;
-    if (pinned) {
+    if ((rc = search_args_ok(ix, q, nq, k, D, I)) != KNN_OK || nq == 0) return rc;
+    if (ix->multi) return multi_search(ix, q, nq, k, D, I);
+    IndexOp op(ix);
+    const bool pinned = (size_t)nq * ix->d * sizeof(float) <= kPinnedSearchBytes;
+    if ((rc = op.begin_host()) == KNN_OK) rc = stage_queries(ix, q, nq, k, pinned);
+    if (rc == KNN_OK) rc = search_locked(ix, ix->hq, nq, k, ix->hd, ix->hi, ix->stream);
+    if (rc == KNN_OK) rc = fetch_results(ix, nq, k, pinned ? ix->pd.get() : D, pinned ? ix->pi.get() : I);
+    if ((rc = op.finish(rc)) == KNN_OK && pinned) {
         std::memcpy(D, ix->pd, (size_t)nq * k * sizeof(float));
         std::memcpy(I, ix->pi, (size_t)nq * k * sizeof(int64_t));
     }
-    return KNN_OK;
+    return rc;
 }
 
 static int range_args_ok(knn_index_t* ix, const float* q, int64_t nq, float radius,
@@ -556,11 +488,9 @@ int knn_range_search_device(knn_index_t* ix, const float* q, int64_t nq, float r
     if ((rc = range_args_ok(ix, q, nq, radius, out)) != KNN_OK) return rc;
     const hipStream_t st = (hipStream_t)stream;
     if (ix->multi) return multi_range_search(ix, q, false, nq, radius, st, out);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
-    if ((rc = range_search_locked(ix, q, nq, radius, st, out)) != KNN_OK) return rc;
-    return fence_end(ix, st);
+    IndexOp op(ix);
+    if ((rc = op.begin(st)) == KNN_OK) rc = range_search_locked(ix, q, nq, radius, st, out);
+    return op.finish(rc);
 }
 
 int knn_range_search(knn_index_t* ix, const float* q, int64_t nq, float radius,
@@ -568,17 +498,10 @@ int knn_range_search(knn_index_t* ix, const float* q, int64_t nq, float radius,
     int rc;
     if ((rc = range_args_ok(ix, q, nq, radius, out)) != KNN_OK) return rc;
     if (ix->multi) return multi_range_search(ix, q, true, nq, radius, nullptr, out);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
-    if (nq > 0) {
-        if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
-        KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice,
-                               ix->stream));
-    }
-    if ((rc = range_search_locked(ix, ix->hq, nq, radius, ix->stream, out)) != KNN_OK) return rc;
-    KNN_HIP(hipStreamSynchronize(ix->stream));
-    return fence_end_synced(ix);
+    IndexOp op(ix);
+    if ((rc = op.begin_host()) == KNN_OK && nq > 0) rc = stage_queries(ix, q, nq, 0);
+    if (rc == KNN_OK) rc = range_search_locked(ix, ix->hq, nq, radius, ix->stream, out);
+    return op.finish(rc);
 }
 
 int64_t knn_range_nq(const knn_range_result_t* r) { return r ? r->nq : KNN_EINVAL; }
@@ -623,33 +546,26 @@ static int filtered_args_ok(knn_index_t* ix, const float* q, int64_t nq, int k, 
 int knn_search_filtered_device(knn_index_t* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
                                int64_t nbits, float* D, int64_t* I, void* stream) {
     int rc;
-    if ((rc = filtered_args_ok(ix, q, nq, k, bitmap, nbits, D, I)) != KNN_OK) return rc;
-    if (nq == 0) return KNN_OK;
+    if ((rc = filtered_args_ok(ix, q, nq, k, bitmap, nbits, D, I)) != KNN_OK || nq == 0) return rc;
     const hipStream_t st = (hipStream_t)stream;
     if (ix->multi) return multi_search_filtered(ix, q, false, nq, k, bitmap, nbits, D, I, st);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
-    if ((rc = filtered_search_locked(ix, q, nq, k, bitmap, nbits, nullptr, D, I, st)) != KNN_OK) return rc;
-    return fence_end(ix, st);
+    IndexOp op(ix);
+    if ((rc = op.begin(st)) == KNN_OK) rc = filtered_search_locked(ix, q, nq, k, bitmap, nbits, nullptr, D, I, st);
+    return op.finish(rc);
 }
 
 int knn_search_filtered(knn_index_t* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
                         int64_t nbits, float* D, int64_t* I) {
     int rc;
-    if ((rc = filtered_args_ok(ix, q, nq, k, bitmap, nbits, D, I)) != KNN_OK) return rc;
-    if (nq == 0) return KNN_OK;
+    if ((rc = filtered_args_ok(ix, q, nq, k, bitmap, nbits, D, I)) != KNN_OK || nq == 0) return rc;
     if (ix->multi) return multi_search_filtered(ix, q, true, nq, k, bitmap, nbits, D, I, nullptr);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
-    if ((rc = filtered_stage_host(ix, q, nq, k, bitmap, &nbits)) != KNN_OK) return rc;
-    if ((rc = filtered_search_locked(ix, ix->hq, nq, k, ix->ft_bits, nbits, nullptr, ix->hd, ix->hi,
-                                     ix->stream)) != KNN_OK) return rc;
-    KNN_HIP(hipMemcpyAsync(D, ix->hd, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    KNN_HIP(hipMemcpyAsync(I, ix->hi, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
-    KNN_HIP(hipStreamSynchronize(ix->stream));
-    return fence_end_synced(ix);
+    IndexOp op(ix);
+    if ((rc = op.begin_host()) == KNN_OK) rc = stage_queries(ix, q, nq, k);
+    if (rc == KNN_OK) rc = stage_bitmap(ix, bitmap, &nbits);
+    if (rc == KNN_OK)
+        rc = filtered_search_locked(ix, ix->hq, nq, k, ix->ft_bits, nbits, nullptr, ix->hd, ix->hi, ix->stream);
+    if (rc == KNN_OK) rc = fetch_results(ix, nq, k, D, I);
+    return op.finish(rc);
 }
 
 int knn_merge_device(const float* cD, const int64_t* cI, int nlists, int64_t nq, int kin, int k,
@@ -699,7 +615,7 @@ int knn_merge_packed_device(const void* packed, int nlists, int64_t nq, int kin,
 int knn_set_timing(knn_index_t* ix, int enable) {
     if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
     if (ix->multi) return multi_set_timing(ix, enable);
-    std::lock_guard<std::mutex> lk(ix->mu);
+    IndexOp op(ix);
     ix->timing = enable != 0;
     ix->ev_used = 0;
     return KNN_OK;
@@ -713,15 +629,14 @@ int knn_set_fence_mode(knn_index_t* ix, int mode) {
         int rc = multi_set_fence_mode(ix, mode);
         if (rc != KNN_OK) return rc;
     }
-    ix->fence_lazy = mode == KNN_FENCE_LAZY;
+    ix->fence.lazy = mode == KNN_FENCE_LAZY;
     return KNN_OK;
 }
 
 int knn_kernel_time(knn_index_t* ix, double* total_ms, int* launches) {
     if (!ix || !total_ms || !launches) KNN_FAIL(KNN_EINVAL, "NULL argument");
     if (ix->multi) return multi_kernel_time(ix, total_ms, launches);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
+    IndexOp op(ix);
     double tot = 0.0;
     for (size_t i = 0; i + 1 < ix->ev_used; i += 2) {
         KNN_HIP(hipEventSynchronize(ix->ev[i + 1]));
@@ -763,12 +678,13 @@ int knn_search_stats2(knn_index_t* ix, int64_t* split_queries, int64_t* fallback
     if (ix->multi)
         return multi_search_stats(ix, split_queries, fallback_queries, second_chance_queries,
                                   max_err_ratio);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
+    IndexOp op(ix);
     int64_t first_fail = 0;
-    const int rc = read_search_stats(ix, split_queries, fallback_queries, &first_fail, max_err_ratio);
+    *fallback_queries = 0;
+    int rc = ix->stat_valid ? op.begin_host() : KNN_OK;     // (no candidate search yet: the GPU is not touched)
+    if (rc == KNN_OK) rc = read_search_stats(ix, split_queries, fallback_queries, &first_fail, max_err_ratio);
     if (second_chance_queries) *second_chance_queries = first_fail - *fallback_queries;
-    return rc;
+    return op.finish_synced(rc);
 }
 
 int knn_last_path(const knn_index_t* ix) {
@@ -779,11 +695,10 @@ int knn_last_path(const knn_index_t* ix) {
 // The count lives on the device (the large-k search never waits for the GPU): reading it waits
 // for the index's last operation.
 static int large_k_fallbacks_one(knn_index* ix, int64_t* n) {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    const int rc = largek_fallbacks(ix, n);
-    if (rc != KNN_OK) return rc;
-    return fence_end_synced(ix);
+    IndexOp op(ix);
+    int rc = ix->lk_fail ? op.begin_host() : KNN_OK;
+    if (rc == KNN_OK) rc = largek_fallbacks(ix, n);
+    return op.finish_synced(rc);
 }
 
 int knn_large_k_fallbacks(const knn_index_t* cix, int64_t* n) {

@@ -21,6 +21,7 @@
 #include "../../include/imgrec_knn.h"
 #include "dev_buf.h"
 #include "knn_kernels.h"
+#include "stream_fence.h"
 
 namespace imgrec {
 
@@ -59,7 +60,7 @@ inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 // The two memory spaces of dev_buf.h: device memory (regrowth reserves half as much again) and
 // page-locked host memory (exact sizes).  The only callers of hipFree / hipHostFree.
-inline int alloc_result(hipError_t e, const char* call) {
+inline int hip_result(hipError_t e, const char* call) {
     if (e == hipSuccess) return KNN_OK;
     set_err("%s failed: %s", call, hipGetErrorString(e));
     return e == hipErrorOutOfMemory ? KNN_ENOMEM : KNN_EHIP;
@@ -67,20 +68,34 @@ inline int alloc_result(hipError_t e, const char* call) {
 struct DeviceSpace {
     static constexpr bool kSlack = true;
     static int alloc(void** p, size_t bytes) {
-        return alloc_result(hipMalloc(p, bytes), "hipMalloc((void**)p, n * sizeof(T))");
+        return hip_result(hipMalloc(p, bytes), "hipMalloc((void**)p, n * sizeof(T))");
     }
     static void free(void* p) { (void)hipFree(p); }
 };
 struct PinnedSpace {
     static constexpr bool kSlack = false;
     static int alloc(void** p, size_t bytes) {
-        return alloc_result(hipHostMalloc(p, bytes, hipHostMallocDefault),
+        return hip_result(hipHostMalloc(p, bytes, hipHostMallocDefault),
                             "hipHostMalloc(p, need_bytes, hipHostMallocDefault)");
     }
     static void free(void* p) { (void)hipHostFree(p); }
 };
 template <typename T> using DevBuf = Buf<T, DeviceSpace>;
 template <typename T> using PinBuf = Buf<T, PinnedSpace>;
+// The stream API of stream_fence.h.
+struct HipStreams {
+    using Stream = hipStream_t;
+    using Event = hipEvent_t;
+    using DeviceScope = DeviceGuard;      // (declared above: the device set, then restored)
+    static int create_event(Event* e) { return hipEventCreateWithFlags(e, hipEventDisableTiming); }
+    static void destroy_event(Event e) { (void)hipEventDestroy(e); }
+    static int record(Event e, Stream s) { return hipEventRecord(e, s); }
+    static int wait(Stream s, Event e) { return hipStreamWaitEvent(s, e, 0); }
+    static int sync_stream(Stream s) { return hipStreamSynchronize(s); }
+    static int sync_device() { return hipDeviceSynchronize(); }
+    static void clear_error() { (void)hipGetLastError(); }
+    static int fail(int e, const char* call) { return hip_result((hipError_t)e, call); }
+};
 
 // ---- launch geometry (knn_plan.cpp; DESIGN.md "Launch plan") ---------------------------------
 struct Plan {
@@ -179,16 +194,8 @@ struct knn_index {
     int64_t last_split_queries = 0;   // queries of the last search on a candidate path
     hipStream_t stream = nullptr;     // the index's own stream (host-pointer entry points)
     std::mutex mu;
-    // Cross-stream ordering: an asynchronous operation records `fence` on its stream when it ends
-    // (KNN_FENCE_EAGER, the default) or only remembers the stream and records the event there
-    // when a later operation arrives on a different stream (KNN_FENCE_LAZY, opt-in); an operation
-    // on a different stream waits for the event (adds before searches, one search's workspace use
-    // before the next's, ...).  Host-synchronous operations leave no fence.
-    hipEvent_t fence = nullptr;
-    hipStream_t fence_stream = nullptr;
-    bool fence_set = false;        // an operation on fence_stream may still run
-    bool fence_recorded = false;   // `fence` already marks its end
-    bool fence_lazy = false;
+    // cross-stream ordering of the index's operations (stream_fence.h; entry points run in an IndexOp)
+    imgrec::Fence<imgrec::HipStreams> fence;
     // search workspace
     DevBuf<float> qpad;
     DevBuf<float> qnorm;
@@ -289,9 +296,16 @@ namespace imgrec {
 const char* last_error();
 int set_metric(knn_index* ix, int metric);
 int set_trained(knn_index* ix, bool trained);
-int fence_begin(knn_index* ix, hipStream_t st);
-int fence_end(knn_index* ix, hipStream_t st);
-int fence_end_synced(knn_index* ix);
+// One operation on an index: its lock, its device and its fence (stream_fence.h OpScope).
+struct IndexOp : OpScope<HipStreams> {
+    explicit IndexOp(knn_index* ix) : OpScope(ix->mu, ix->device, ix->fence, ix->stream) {}
+};
+// The host forms' staging on the index's own stream: nq queries up into hq (through the page-locked
+// pq when `pinned`, which also reserves pd / pi) with room for nq x k results in hd / hi when k > 0;
+// the bitmap's bytes that can matter (*nbits is lowered to ntotal) up into ft_bits; results down.
+int stage_queries(knn_index* ix, const float* q, int64_t nq, int k, bool pinned = false);
+int stage_bitmap(knn_index* ix, const uint8_t* bitmap, int64_t* nbits);
+int fetch_results(knn_index* ix, int64_t nq, int k, float* D, int64_t* I);
 // The per-row corpus arrays with their row strides in bytes, in allocation order: the only place
 // that lists them.  Fills cols with the live ones (the split and int8 copies once materialised, the
 // bf16 copy where enabled: what follows every add, regrowth and removal) and returns their number;
@@ -303,8 +317,6 @@ int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st);
 int ensure_split(knn_index* ix, hipStream_t st);
 int ensure_i8(knn_index* ix, hipStream_t st);
 int create_single(int d, int metric, int device, knn_index** out);
-int filtered_stage_host(knn_index* ix, const float* q, int64_t nq, int k, const uint8_t* bitmap,
-                        int64_t* nbits);
 void free_single(knn_index* ix);
 // knn_search.cpp
 int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
@@ -326,7 +338,8 @@ bool stream_lists_ok(const knn_index* ix, int64_t nq);
 int stream_splits(const knn_index* ix);
 hipError_t launch_stream_lists(const knn_index* ix, const float* qpad, const float* qnorm, int64_t nq,
                                int metric, int sp, float* cd, int64_t* ci, hipStream_t st);
-// queries the last large-k search sent to the exact scan (a device count; waits for the index)
+// queries the last large-k search sent to the exact scan (a device count: read on the index's own
+// stream, which it synchronises; the caller holds a begun host scope when lk_fail exists)
 int largek_fallbacks(knn_index* ix, int64_t* n);
 // merge of nlists sorted per-shard lists for KNN_MAX_K < k (nlists * kin <= 8192; labels < 2^32)
 hipError_t launch_merge_large(const float* cD, const int64_t* cI, int nlists, int64_t nq, int kin,

@@ -477,8 +477,8 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
         float* cur = ca;
         float* nxt = cb;
         {
-            std::lock_guard<std::mutex> lk(w->mu);
-            int rc = w->begin(st);
+            HandoffOp op(w);
+            int rc = op.begin(st);
             if (rc != KNN_OK) return rc;
             if (init) {
                 KNN_HIP(hipMemcpyAsync(cur, init, kd * sizeof(float), hipMemcpyHostToDevice, st));
@@ -503,7 +503,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
                 hipLaunchKernelGGL(kmeans_normalize_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, cur, k, d);
                 KNN_HIP(hipGetLastError());
             }
-            if ((rc = w->end(st)) != KNN_OK) return rc;
+            if ((rc = op.finish(KNN_OK)) != KNN_OK) return rc;
         }
         const clk::time_point t0 = clk::now();
         double t_search = 0.0, obj = 0.0;
@@ -511,8 +511,8 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
             const clk::time_point ts = clk::now();
             int nsplit = 0;
             {
-                std::lock_guard<std::mutex> lk(w->mu);
-                int rc = w->begin(st);
+                HandoffOp op(w);
+                int rc = op.begin(st);
                 if (rc != KNN_OK) return rc;
                 if ((rc = step_locked(w, x, n, d, cur, k, flags, as, di, nxt, cnt_d, obj_d,
                                       st, evs.e)) != KNN_OK)
@@ -531,7 +531,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
                     hipLaunchKernelGGL(kmeans_normalize_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, nxt, k, d);
                     KNN_HIP(hipGetLastError());
                 }
-                if ((rc = w->end(st)) != KNN_OK) return rc;
+                if ((rc = op.finish(KNN_OK)) != KNN_OK) return rc;
                 float ms[3] = {0.f, 0.f, 0.f};
                 for (int e = 0; e < 3; ++e) KNN_HIP(hipEventElapsedTime(&ms[e], evs.e[e], evs.e[e + 1]));
                 double* s = &stats[(size_t)it * KMEANS_STATS_PER_ITER];
@@ -588,12 +588,10 @@ int kmeans_step_device(const float* x, int64_t n, int d, const float* centroids,
     KNN_HIP(hipGetDevice(&device));
     Workspace* w = per_device<Workspace>(device);
     hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = w->begin(st)) != KNN_OK) return rc;
-    if ((rc = step_locked(w, x, n, d, centroids, k, flags, assign, dist, new_centroids, counts, obj, st,
-                          nullptr)) != KNN_OK)
-        return rc;
-    return w->end(st);
+    HandoffOp op(w);
+    if ((rc = op.begin(st)) == KNN_OK)
+        rc = step_locked(w, x, n, d, centroids, k, flags, assign, dist, new_centroids, counts, obj, st, nullptr);
+    return op.finish(rc);
 }
 
 int kmeans_split_device(float* centroids, int k, int d, int64_t* counts_host, int* nsplit, void* stream) {
@@ -614,10 +612,9 @@ int kmeans_split_device(float* centroids, int k, int d, int64_t* counts_host, in
     KNN_HIP(hipGetDevice(&device));
     Workspace* w = per_device<Workspace>(device);
     hipStream_t st = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = w->begin(st)) != KNN_OK) return rc;
-    if ((rc = split_locked(w, centroids, k, d, counts_host, nsplit, st)) != KNN_OK) return rc;
-    return w->end(st);
+    HandoffOp op(w);
+    if ((rc = op.begin(st)) == KNN_OK) rc = split_locked(w, centroids, k, d, counts_host, nsplit, st);
+    return op.finish(rc);
 }
 
 int kmeans_train_device(const float* x_dev, int64_t n, int d, int k, const kmeans_params_t* params,

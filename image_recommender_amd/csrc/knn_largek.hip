@@ -491,8 +491,6 @@ hipError_t launch_stream_lists(const knn_index* ix, const float* qpad, const flo
 int largek_fallbacks(knn_index* ix, int64_t* n) {
     *n = 0;
     if (!ix->lk_fail) return KNN_OK;
-    int rc;
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
     int v = 0;
     KNN_HIP(hipMemcpyAsync(&v, ix->lk_fail + kLKChunk + 1, sizeof(int), hipMemcpyDeviceToHost, ix->stream));
     KNN_HIP(hipStreamSynchronize(ix->stream));

@@ -258,10 +258,9 @@ int multi_remove_ids(knn_index* ix, const uint8_t* bitmap, int64_t nbits, int64_
     for (size_t s = 0; s < m->shards.size(); ++s) {
         knn_index* sh = m->shards[s];
         if (sh->ntotal == 0) continue;
-        DeviceGuard g(sh->device);
-        std::lock_guard<std::mutex> lks(sh->mu);
+        IndexOp ops(sh);
         const hipStream_t ss = sh->stream;
-        if ((rc = fence_begin(sh, ss)) != KNN_OK) return rc;
+        if ((rc = ops.begin_host()) != KNN_OK) return rc;
         if ((rc = sh->ft_bits.reserve(nw * 4)) != KNN_OK) return rc;
         if ((rc = sh->rm_pref.reserve(nw)) != KNN_OK) return rc;
         KNN_HIP(hipMemcpyAsync(sh->ft_bits, words.data(), nw * 4, hipMemcpyHostToDevice, ss));
@@ -272,8 +271,7 @@ int multi_remove_ids(knn_index* ix, const uint8_t* bitmap, int64_t nbits, int64_
         KNN_HIP(launch_renumber_labels(m->per[s].lmap, sh->ntotal,
                                        reinterpret_cast<const uint32_t*>(sh->ft_bits.get()),
                                        sh->rm_pref, nbits, removed, ss));
-        KNN_HIP(hipStreamSynchronize(ss));
-        if ((rc = fence_end_synced(sh)) != KNN_OK) return rc;
+        if ((rc = ops.finish(KNN_OK)) != KNN_OK) return rc;
     }
     std::vector<knn_multi::Run> runs;
     std::vector<int64_t> local(m->shards.size(), 0);
@@ -305,32 +303,32 @@ namespace {
 
 // Every shard searches q (device pointer on the first device, ready when m->ready fires) into the
 // gather buffer; the first device's stream `st` then merges into D, I.  With `filtered`, the
-// search among the rows the bitmap `bits` (first device, global rows) selects.
+// search among the rows the bitmap `bits` (first device, global rows; nbits <= ntotal) selects.
 int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                    hipStream_t st, bool filtered = false, const uint8_t* bits = nullptr,
                    int64_t nbits = 0) {
     knn_multi* m = M(ix);
     const int ndev = (int)m->shards.size();
     const size_t nk = (size_t)nq * k;
+    if (ix->ntotal == 0 || (filtered && nbits == 0)) {       // no row to search: the empty rows
+        KNN_HIP(launch_fill_empty(D, I, nq * (int64_t)k, ix->metric == KNN_METRIC_L2 ? 1 : 0, st));
+        return KNN_OK;
+    }
     // the k > KNN_MAX_K merges pack a label into 32 bits (include/imgrec_knn.h knn_merge_device)
     if (k > KNN_MAX_K && ix->ntotal + ix->id_offset > (int64_t(1) << 32))
         KNN_FAIL(KNN_EINVAL, "k = %d > %d over shards: labels must stay below 2^32, ntotal + id_offset = %lld",
                  k, KNN_MAX_K, (long long)(ix->ntotal + ix->id_offset));
-    int rc;
-    {
-        DeviceGuard g(ix->device);
-        if ((rc = m->gD.reserve(nk * ndev)) != KNN_OK) return rc;
-        if ((rc = m->gI.reserve(nk * ndev)) != KNN_OK) return rc;
-        KNN_HIP(hipEventRecord(m->ready, st));
-    }
+    int rc;                                      // (the caller's scope has set the first device)
+    if ((rc = m->gD.reserve(nk * ndev)) != KNN_OK) return rc;
+    if ((rc = m->gI.reserve(nk * ndev)) != KNN_OK) return rc;
+    KNN_HIP(hipEventRecord(m->ready, st));
     for (int s = 0; s < ndev; ++s) {
         knn_index* sh = m->shards[s];
         const bool local = sh->device == ix->device && !m->force_remote;
-        DeviceGuard g(sh->device);
-        std::lock_guard<std::mutex> lk(sh->mu);
+        IndexOp ops(sh);
         const hipStream_t ss = sh->stream;
         KNN_HIP(hipStreamWaitEvent(ss, m->ready, 0));
-        if ((rc = fence_begin(sh, ss)) != KNN_OK) return rc;
+        if ((rc = ops.begin(ss)) != KNN_OK) return rc;
         const float* qs = q;
         float* ds = m->gD + s * nk;
         int64_t* is = m->gI + s * nk;
@@ -364,10 +362,9 @@ int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, i
             KNN_HIP(hipMemcpyPeerAsync(m->gI + s * nk, ix->device, is, sh->device,
                                        nk * sizeof(int64_t), ss));
         }
-        if ((rc = fence_end(sh, ss)) != KNN_OK) return rc;
+        if ((rc = ops.finish(KNN_OK)) != KNN_OK) return rc;
         KNN_HIP(hipEventRecord(m->per[s].done, ss));
     }
-    DeviceGuard g(ix->device);
     for (int s = 0; s < ndev; ++s) KNN_HIP(hipStreamWaitEvent(st, m->per[s].done, 0));
     const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
     if (k > KNN_MAX_K) {
@@ -383,70 +380,33 @@ int fan_out_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, i
 
 int multi_search_device(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                         hipStream_t st) {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    int rc;
-    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
-    if (ix->ntotal == 0) {
-        KNN_HIP(launch_fill_empty(D, I, nq * (int64_t)k, ix->metric == KNN_METRIC_L2 ? 1 : 0, st));
-        return fence_end(ix, st);
-    }
-    if ((rc = fan_out_search(ix, q, nq, k, D, I, st)) != KNN_OK) return rc;
-    return fence_end(ix, st);
+    IndexOp op(ix);
+    int rc = op.begin(st);
+    if (rc == KNN_OK) rc = fan_out_search(ix, q, nq, k, D, I, st);
+    return op.finish(rc);
 }
 
 int multi_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I) {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    int rc;
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
-    if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
-    if ((rc = ix->hd.reserve((size_t)nq * k)) != KNN_OK) return rc;
-    if ((rc = ix->hi.reserve((size_t)nq * k)) != KNN_OK) return rc;
-    KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice,
-                           ix->stream));
-    if (ix->ntotal == 0) {
-        KNN_HIP(launch_fill_empty(ix->hd, ix->hi, nq * (int64_t)k,
-                                  ix->metric == KNN_METRIC_L2 ? 1 : 0, ix->stream));
-    } else if ((rc = fan_out_search(ix, ix->hq, nq, k, ix->hd, ix->hi, ix->stream)) != KNN_OK) {
-        return rc;
-    }
-    KNN_HIP(hipMemcpyAsync(D, ix->hd, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost,
-                           ix->stream));
-    KNN_HIP(hipMemcpyAsync(I, ix->hi, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost,
-                           ix->stream));
-    KNN_HIP(hipStreamSynchronize(ix->stream));
-    return fence_end_synced(ix);
+    IndexOp op(ix);
+    int rc = op.begin_host();
+    if (rc == KNN_OK) rc = stage_queries(ix, q, nq, k);        // (pageable copies: knn_search's pinned path is not taken)
+    if (rc == KNN_OK) rc = fan_out_search(ix, ix->hq, nq, k, ix->hd, ix->hi, ix->stream);
+    if (rc == KNN_OK) rc = fetch_results(ix, nq, k, D, I);
+    return op.finish(rc);
 }
 
 int multi_search_filtered(knn_index* ix, const float* q, bool q_on_host, int64_t nq, int k,
                           const uint8_t* bitmap, int64_t nbits, float* D, int64_t* I, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    if (q_on_host) st = ix->stream;
-    const int kmetric = ix->metric == KNN_METRIC_L2 ? 1 : 0;
-    int rc;
-    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
-    float* Dd = D;
-    int64_t* Id = I;
-    if (q_on_host) {
-        if ((rc = filtered_stage_host(ix, q, nq, k, bitmap, &nbits)) != KNN_OK) return rc;
-        q = ix->hq;
-        bitmap = ix->ft_bits;
-        Dd = ix->hd;
-        Id = ix->hi;
-    }
+    IndexOp op(ix);
+    int rc = q_on_host ? op.begin_host() : op.begin(st);
+    if (rc == KNN_OK && q_on_host) rc = stage_queries(ix, q, nq, k);
+    if (rc == KNN_OK && q_on_host) rc = stage_bitmap(ix, bitmap, &nbits);
+    if (rc != KNN_OK) return rc;
     nbits = std::min(nbits, ix->ntotal);         // bits at or past ntotal are ignored
-    if (ix->ntotal == 0 || nbits == 0) {
-        KNN_HIP(launch_fill_empty(Dd, Id, nq * (int64_t)k, kmetric, st));
-    } else if ((rc = fan_out_search(ix, q, nq, k, Dd, Id, st, true, bitmap, nbits)) != KNN_OK) {
-        return rc;
-    }
-    if (!q_on_host) return fence_end(ix, st);
-    KNN_HIP(hipMemcpyAsync(D, Dd, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-    KNN_HIP(hipMemcpyAsync(I, Id, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    KNN_HIP(hipStreamSynchronize(st));
-    return fence_end_synced(ix);
+    rc = q_on_host ? fan_out_search(ix, ix->hq, nq, k, ix->hd, ix->hi, op.stream(), true, ix->ft_bits, nbits)
+                   : fan_out_search(ix, q, nq, k, D, I, st, true, bitmap, nbits);
+    if (rc == KNN_OK && q_on_host) rc = fetch_results(ix, nq, k, D, I);
+    return op.finish(rc);
 }
 
 // Range search: every shard runs the single-device range search on its own device and stream, one
@@ -457,15 +417,13 @@ int multi_search_filtered(knn_index* ix, const float* q, bool q_on_host, int64_t
 int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq, float radius,
                        hipStream_t st, knn_range_result** out) {
     knn_multi* m = M(ix);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
+    IndexOp op(ix);
     const int ndev = (int)m->shards.size();
-    if (q_on_host) st = ix->stream;
-    int rc;
-    if ((rc = fence_begin(ix, st)) != KNN_OK) return rc;
+    int rc = q_on_host ? op.begin_host() : op.begin(st);
+    if (rc != KNN_OK) return rc;
+    st = op.stream();
     if (q_on_host && nq > 0) {
-        if ((rc = ix->hq.reserve((size_t)nq * ix->d)) != KNN_OK) return rc;
-        KNN_HIP(hipMemcpyAsync(ix->hq, q, (size_t)nq * ix->d * sizeof(float), hipMemcpyHostToDevice, st));
+        if ((rc = stage_queries(ix, q, nq, 0)) != KNN_OK) return rc;
         q = ix->hq;
     }
     KNN_HIP(hipEventRecord(m->ready, st));
@@ -481,12 +439,11 @@ int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq
         knn_index* sh = m->shards[s];
         ShardHits& h = hits[s];
         const bool local = sh->device == ix->device && !m->force_remote;
-        DeviceGuard gs(sh->device);
-        std::lock_guard<std::mutex> lks(sh->mu);
+        IndexOp ops(sh);
         const hipStream_t ss = sh->stream;
         int r;
         KNN_HIP(hipStreamWaitEvent(ss, m->ready, 0));
-        if ((r = fence_begin(sh, ss)) != KNN_OK) return r;
+        if ((r = ops.begin_host()) != KNN_OK) return r;
         const float* qs = q;
         if (!local && nq > 0) {
             if ((r = m->per[s].sq.reserve((size_t)nq * ix->d)) != KNN_OK) return r;
@@ -512,7 +469,7 @@ int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq
         range_result_free(res);
         if (e != hipSuccess || e2 != hipSuccess)
             KNN_FAIL(KNN_EHIP, "range search shard %d: %s", s, hipGetErrorString(e != hipSuccess ? e : e2));
-        return fence_end_synced(sh);
+        return ops.finish_synced(KNN_OK);
     };
     {
         std::vector<std::thread> th;
@@ -555,9 +512,8 @@ int multi_range_search(knn_index* ix, const float* q, bool q_on_host, int64_t nq
             I[(size_t)lims[i] + e] = seg[e].first.second;
         }
     }
-    if ((rc = range_result_from_host(ix->device, nq, lims.data(), D.data(), I.data(), st, out)) != KNN_OK)
-        return rc;
-    return q_on_host ? fence_end_synced(ix) : fence_end(ix, st);
+    // (the upload synchronises st: the host form has nothing left to wait for)
+    return op.finish_synced(range_result_from_host(ix->device, nq, lims.data(), D.data(), I.data(), st, out));
 }
 
 int multi_set_metric(knn_index* ix, int metric) {
@@ -599,7 +555,7 @@ int multi_kernel_time(knn_index* ix, double* total_ms, int* launches) {
 int multi_set_fence_mode(knn_index* ix, int mode) {
     for (knn_index* sh : M(ix)->shards) {
         std::lock_guard<std::mutex> lk(sh->mu);
-        sh->fence_lazy = mode == KNN_FENCE_LAZY;
+        sh->fence.lazy = mode == KNN_FENCE_LAZY;
     }
     return KNN_OK;
 }

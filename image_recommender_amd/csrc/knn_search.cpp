@@ -595,7 +595,8 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
     return KNN_OK;
 }
 
-// Totals of the last search's candidate chunks (waits for that search to finish).
+// Totals of the last search's candidate chunks (read on the index's own stream, which it
+// synchronises: while stat_valid the caller holds a begun host scope).
 int read_search_stats(knn_index* ix, int64_t* split_q, int64_t* fallback_q, int64_t* first_fail,
                       float* ratio) {
     *split_q = ix->last_split_queries;
@@ -603,8 +604,6 @@ int read_search_stats(knn_index* ix, int64_t* split_q, int64_t* fallback_q, int6
     if (first_fail) *first_fail = 0;
     if (ratio) *ratio = 0.f;
     if (!ix->stat_valid) return KNN_OK;
-    int rc;
-    if ((rc = fence_begin(ix, ix->stream)) != KNN_OK) return rc;
     int acc[4] = {0, 0, 0, 0};
     KNN_HIP(hipMemcpyAsync(acc, ix->stat + 8, sizeof(acc), hipMemcpyDeviceToHost, ix->stream));
     KNN_HIP(hipStreamSynchronize(ix->stream));

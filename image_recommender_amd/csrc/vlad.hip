@@ -415,10 +415,9 @@ int encode_device_impl(const VladArgs& a, int32_t* nn_idx, float* nn_dist, hipSt
     int device = 0;
     KNN_HIP(hipGetDevice(&device));
     Workspace* w = per_device<Workspace>(device);
-    std::lock_guard<std::mutex> lk(w->mu);
-    if ((rc = w->begin(st)) != KNN_OK) return rc;
-    if ((rc = encode_locked(w, a, ct, ntiles, nn_idx, nn_dist, st)) != KNN_OK) return rc;
-    return w->end(st);
+    HandoffOp op(w);
+    if ((rc = op.begin(st)) == KNN_OK) rc = encode_locked(w, a, ct, ntiles, nn_idx, nn_dist, st);
+    return op.finish(rc);
 }
 
 }  // namespace

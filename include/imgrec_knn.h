@@ -44,7 +44,9 @@
  *     (KNN_FENCE_LAZY) records the event only when the stream changes: one stream used back to
  *     back then records none (~6 us of GPU time per call saved on MI355X), but the previous
  *     call's stream must stay valid until the next call on the index, and the wait then also
- *     covers work the caller queued on that stream in between.
+ *     covers work the caller queued on that stream in between.  A call that fails keeps this
+ *     order too: what it had enqueued is waited for like a successful call's, and a failing
+ *     host-pointer call returns with no copy into the caller's arrays still in flight.
  *   - Vectors are row-major float32, n rows × d.  Labels are int64.  Result rows are sorted by
  *     ascending distance (L2) or descending inner product (IP/COSINE); exact ties are broken by the
  *     smaller label.  When fewer than k vectors exist, the tail of a result row holds label -1 and

@@ -333,3 +333,81 @@ def test_fence_across_destroyed_and_switched_streams(faiss, lazy):
     np.testing.assert_array_equal(I0, I2)
     np.testing.assert_array_equal(outs[0][0].cpu().numpy(), outs[2][0].cpu().numpy())
     check_knn(outs[2][0].cpu().numpy()[::10], I2[::10], xb, xq[::10], 10, "l2", min_exact_frac=0.5)
+
+
+# ---- one index through every operation kind, the stream changing at every step -------------------------
+SEQ_D, SEQ_N, SEQ_NQ, SEQ_K = 64, 4096, 8, 10
+
+
+def _seq_data():
+    x = mixture(SEQ_N + SEQ_NQ, SEQ_D, centres=16, seed=77)
+    xb, xq = np.ascontiguousarray(x[:SEQ_N]), np.ascontiguousarray(x[SEQ_N:])
+    d2 = ((xq[:, None, :].astype(np.float64) - xb[None, :, :]) ** 2).sum(-1)
+    radius = float(np.median(np.sort(d2, axis=1)[:, 30]))       # a few dozen rows per query
+    return xb, xq, radius
+
+
+def _op_sequence(faiss, lazy, switch, devices=None):
+    """add_device (two calls), search_device, range_search_device, search_filtered_device, host
+    remove_ids, host search, certificate_stats, search_device: with `switch` each device form runs on
+    the other of two streams than the step before it and nothing waits in between; without it,
+    everything runs on one stream with a device synchronisation after every step.  Returns every
+    output as bytes (and the stats dict), read after the last step."""
+    import torch
+    xb, xq, radius = _seq_data()
+    idx = faiss.IndexFlatL2(SEQ_D, devices=devices) if devices else faiss.IndexFlatL2(SEQ_D)
+    idx.set_fence_mode(lazy)
+    halves = [torch.from_numpy(xb[:SEQ_N // 2]).cuda(), torch.from_numpy(xb[SEQ_N // 2:]).cuda()]
+    q = torch.from_numpy(xq).cuda()
+    bits = torch.from_numpy(np.packbits(np.arange(SEQ_N) % 3 == 0, bitorder="little")).cuda()
+    outs = [(torch.full((SEQ_NQ, SEQ_K), float("nan"), dtype=torch.float32, device="cuda"),
+             torch.full((SEQ_NQ, SEQ_K), -7, dtype=torch.int64, device="cuda")) for _ in range(3)]
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()       # both alive to the end (the lazy fence)
+    A, B = (sa.cuda_stream, sb.cuda_stream) if switch else (sa.cuda_stream, sa.cuda_stream)
+    torch.cuda.synchronize()
+
+    def step():
+        if not switch:
+            torch.cuda.synchronize()
+
+    idx.add_device(halves[0].data_ptr(), SEQ_N // 2, B); step()
+    idx.add_device(halves[1].data_ptr(), SEQ_N // 2, A); step()                                 # 1
+    idx.search_device(q.data_ptr(), SEQ_NQ, SEQ_K, outs[0][0].data_ptr(), outs[0][1].data_ptr(), B); step()  # 2
+    rng = idx.range_search_device(q.data_ptr(), SEQ_NQ, radius, A); step()                      # 3
+    idx.search_filtered_device(q.data_ptr(), SEQ_NQ, SEQ_K, bits.data_ptr(), SEQ_N,
+                               outs[1][0].data_ptr(), outs[1][1].data_ptr(), B); step()         # 4
+    removed = idx.remove_ids(np.arange(0, SEQ_N, 41)[:100]); step()                             # 5
+    hD, hI = idx.search(xq, SEQ_K); step()                                                      # 6
+    stats = idx.certificate_stats(); step()                                                     # 7
+    idx.search_device(q.data_ptr(), SEQ_NQ, SEQ_K, outs[2][0].data_ptr(), outs[2][1].data_ptr(), A)          # 8
+    torch.cuda.synchronize()
+    lims, rD, rI = rng.to_host()
+    assert removed == 100 and idx.ntotal == SEQ_N - 100
+    per_query = np.diff(lims)
+    assert 10 <= per_query.mean() <= 200, per_query
+    got = {"range": [lims, rD, rI], "host": [hD, hI]}
+    for name, (D, I) in zip(("search", "filtered", "last"), outs):
+        got[name] = [D.cpu().numpy(), I.cpu().numpy()]
+    assert (got["filtered"][1] % 3 == 0).all() and (got["search"][1] >= 0).all()
+    return {k: [v.tobytes() for v in vs] for k, vs in got.items()}, stats
+
+
+@pytest.fixture(scope="module")
+def seq_reference(faiss):
+    return _op_sequence(faiss, lazy=False, switch=False)
+
+
+@pytest.mark.parametrize("lazy", [False, True])
+def test_every_operation_kind_with_the_stream_changing_at_every_step(faiss, seq_reference, lazy):
+    got, stats = _op_sequence(faiss, lazy=lazy, switch=True)
+    assert got == seq_reference[0]
+    assert stats == seq_reference[1]
+
+
+@pytest.mark.parametrize("lazy", [False, True])
+def test_every_operation_kind_on_two_forced_remote_shards(faiss, seq_reference, lazy, monkeypatch):
+    """The same sequence on a two-shard index on one device, its shards on the staging + peer-copy
+    path: byte-equal to the single index (the certificate counts are per shard, so only read)."""
+    monkeypatch.setenv("IMGREC_MULTI_FORCE_REMOTE", "1")    # read when the index is created
+    got, _ = _op_sequence(faiss, lazy=lazy, switch=True, devices=[0, 0])
+    assert got == seq_reference[0]

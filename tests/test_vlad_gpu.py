@@ -234,3 +234,40 @@ def test_neighbours_agree_with_the_flat_index(gpu, runs, name):
     ordered = clear & (np.diff(Dt, axis=1) > Et[:, :-1] + Et[:, 1:]).all(1)
     assert ordered.mean() > 0.5
     np.testing.assert_array_equal(I[ordered], idx[ordered].astype(np.int64))
+
+
+def test_encode_device_alternating_on_two_streams(gpu):
+    """Six encodings alternating between two streams share the per-device workspace (code norms,
+    neighbour lists) through its stream hand-off (csrc/dev_workspace.h over csrc/stream_fence.h): each
+    equals, byte for byte, the same encoding called alone on one stream.  Every call has descriptors
+    of its own, so a call that overtook its predecessor's use of the workspace would show."""
+    import torch
+    from image_recommender_amd.vlad import SoftVLAD
+    from tests.datagen import mixture
+    nimg, per, d, k, nn, calls = 4, 50, 128, 16, 4, 6
+    data = mixture(k + calls * nimg * per, d, centres=k, seed=41)
+    enc = SoftVLAD(data[:k], nn=nn, sigma=1.0)
+    xs = [torch.from_numpy(np.ascontiguousarray(data[k + c * nimg * per:k + (c + 1) * nimg * per])).cuda()
+          for c in range(calls)]
+    off = torch.arange(0, nimg * per + 1, per, dtype=torch.int64).cuda()
+    enc.codebook_device()
+    one = torch.cuda.Stream()
+    torch.cuda.synchronize()
+
+    def run(streams, sync):
+        outs = [torch.full((nimg, enc.dim), float("nan"), dtype=torch.float32, device="cuda") for _ in xs]
+        torch.cuda.synchronize()
+        for c, (x, out) in enumerate(zip(xs, outs)):
+            enc.encode_device(x.data_ptr(), off.data_ptr(), nimg, nimg * per, out.data_ptr(),
+                              stream=streams[c % len(streams)].cuda_stream)
+            if sync:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        return [o.cpu().numpy() for o in outs]
+
+    alone = run([one], True)
+    assert all(np.isfinite(a).all() for a in alone)
+    assert len({a.tobytes() for a in alone}) == calls
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    for got, want in zip(run([a, b], False), alone):
+        assert got.tobytes() == want.tobytes()

@@ -27,6 +27,12 @@ KMEANS_STATS_PER_ITER = 8
 VLAD_RAW = 1                  # include/imgrec_vlad.h
 VLAD_MAX_NN = 8
 VLAD_MAX_D = 16384
+VLADENC_MODEL_OUTPUT = 1      # include/imgrec_vladenc.h
+VLADENC_MAX_LAYERS = 8
+VLADENC_MAX_WIDTH = 4096
+VLADENC_MAX_IN = 1 << 20
+VLADENC_CHUNK_ROWS = 128
+VLADENC_SUPER_ROWS = 2048
 
 
 class KmeansParams(C.Structure):
@@ -99,6 +105,13 @@ SIGNATURES = {
     # imgrec_vlad.h
     "vlad_encode_device": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp]),
     "vlad_encode": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _i]),
+    # imgrec_vladenc.h
+    "vladenc_create": (_i, [_i, _pi, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _f, _i,
+                            C.POINTER(_vp)]),
+    "vladenc_free": (_i, [_vp]),
+    "vladenc_widths": (_i, [_vp, _pi, _pi]),
+    "vladenc_forward_device": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "vladenc_forward": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     # imgrec_color.h
     "color_hist_device": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "color_hist_host": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _vp]),

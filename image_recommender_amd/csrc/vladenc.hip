@@ -1,0 +1,429 @@
+// vladenc.hip — the forward pass of the SIFT-VLAD MLP encoder (include/imgrec_vladenc.h; the
+// reference's SIFTVLADEncoder and compute_vectors, vector_scripts/create_sift_vector.py:59-77, 514-521).
+//
+// A batch runs in chunks of VLADENC_SUPER_ROWS rows; inside a chunk a layer is three launches on the
+// caller's stream per group of row tiles (as many as keep the partial sums within 64 MiB: one tile
+// of 128 rows for the reference's first layer, the whole chunk for its later layers):
+//   1. vladenc_linear_kernel<..>  grid = feature tiles (256) x depth splits x row tiles.  The tile of
+//                                 rows_tile.h turned to a plain GEMM: the weight rows are the MFMA's A
+//                                 rows, the batch rows its columns, 32 depth columns per stage through
+//                                 LDS (row stride kLDK, load_row4's guarded loads for ragged K, N and
+//                                 batch), the next stage's global loads in registers during the MFMAs.
+//                                 A workgroup streams only its split's stages and leaves its
+//                                 accumulators, one fmaf chain per (row, feature), in the workspace as
+//                                 part[split][feature][row]: a lane owns a batch row, so a register's
+//                                 64 stores are two 128-byte runs.  Two shapes of the same chain: 128
+//                                 batch rows (4 x 2 waves, 2 x 2 accumulators each) and, for chunks
+//                                 of at most 32 rows, 32 batch rows (8 x 1 waves, one accumulator
+//                                 each), which spends a quarter of the MFMA work on the B = 1 weight
+//                                 stream.  The chain of an element is the same in both, so which one
+//                                 runs changes no byte.
+//   2. vladenc_reduce_kernel      a thread per (feature, row): the splits' partial sums added in
+//                                 ascending order, then the bias, in place over split 0.  Its loads
+//                                 are contiguous and 16 are in flight per thread: at B = 1 the 147
+//                                 partial sums of a feature would otherwise be 147 round trips.
+//   3. vladenc_finish_kernel      a workgroup per row: LayerNorm and Mish or, on the last layer, the
+//                                 two normalisations (float64 sums in the fixed order the header
+//                                 documents), the activation to the workspace (or `out`) and to `hidden`.
+//
+// The split rule, the chunk rule and the argument checks are vladenc_args.h (host-checked under
+// sanitizers).  At the reference's widths the first layer is 3 tiles x 147 splits = 441 workgroups
+// whatever the batch; the later layers are 2 x 5 and 1 x 2.
+//
+// LDS: (256 + 128) x 36 floats = 55 KB, (256 + 32) x 36 = 41 KB for the narrow shape; the finish
+// kernel holds a row (16 KB).  Registers per kernel: profiles/vladenc/.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+#include "../../include/imgrec_vladenc.h"
+#include "dev_workspace.h"
+#include "rows_tile.h"
+#include "vladenc_args.h"
+
+struct vladenc {
+    int nlayers = 0;
+    int widths[VLADENC_MAX_LAYERS + 1] = {};
+    int hsum = 0;                // the hidden widths' sum: a row of `hidden`
+    int hmax = 1;                // the widest hidden layer
+    float eps = 0.f;
+    int device = 0;
+    imgrec::DevBuf<float> W[VLADENC_MAX_LAYERS], b[VLADENC_MAX_LAYERS], g[VLADENC_MAX_LAYERS], be[VLADENC_MAX_LAYERS];
+};
+
+namespace imgrec {
+namespace {
+
+static_assert(kEncStage == kBK && kEncFeat == kBN, "the split rule counts this tile's stages and feature tiles");
+
+enum { kHidden = 0, kModelOutput = 1, kStored = 2 };     // what the finish kernel does after the bias
+
+// Waves per SIMD the 128-row shape is compiled for.  4 = two workgroups per CU: 128 VGPRs with 14 of
+// its 158 spilled to scratch, and still 6 % faster at B = 1024 than one workgroup per CU
+// (-DVLADENC_WIDE_WAVES=1; profiles/vladenc/), because a neighbour's MFMAs cover a workgroup's
+// first load, barriers and stores.
+#ifndef VLADENC_WIDE_WAVES
+#define VLADENC_WIDE_WAVES 4
+#endif
+
+// FW x PW waves over the features and the batch rows, FA x PB accumulators of 32 x 32 per wave
+template <int FW, int PW, int FA, int PB>
+__global__ void __launch_bounds__(kNT, FA * PB == 4 ? VLADENC_WIDE_WAVES : 1)
+vladenc_linear_kernel(const float* __restrict__ x, int m, int K, const float* __restrict__ W, int N, int per,
+                      int stages, int vec_x, int vec_w, float* __restrict__ part) {
+    constexpr int BN = FW * FA * 32, BM = PW * PB * 32, R = BN + BM, LD4 = (R * kQ + kNT - 1) / kNT;
+    static_assert(FW * PW * 64 == kNT && BN == kBN, "eight waves, one feature tile");
+    __shared__ __attribute__((aligned(16))) float stage[R * kLDK];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int wf = wave % FW, wp = wave / FW;
+    const int f0 = blockIdx.x * BN, split = blockIdx.y, p0 = blockIdx.z * BM;
+    const int s0 = split * per, s1 = min(s0 + per, stages);
+
+    float4 pre[LD4];
+    auto fetch = [&](int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int it = 0; it < LD4; ++it) {
+            const int idx = tid + it * kNT, row = idx / kQ, col = s * kBK + 4 * (idx % kQ);
+            if (R * kQ % kNT == 0 || idx < R * kQ)
+                pre[it] = row < BN ? load_row4(W, (int64_t)f0 + row, N, K, col, vec_w)
+                                   : load_row4(x, (int64_t)p0 + (row - BN), m, K, col, vec_x);
+        }
+    };
+    auto store = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int it = 0; it < LD4; ++it) {
+            const int idx = tid + it * kNT;
+            if (R * kQ % kNT == 0 || idx < R * kQ)
+                *reinterpret_cast<float4*>(stage + (idx / kQ) * kLDK + 4 * (idx % kQ)) = pre[it];
+        }
+    };
+
+    f32x16 acc[FA][PB];
+#pragma unroll
+    for (int a = 0; a < FA; ++a)
+#pragma unroll
+        for (int b = 0; b < PB; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+    fetch(s0);
+    store();
+    __syncthreads();
+    for (int s = s0; s < s1; ++s) {
+        if (s + 1 < s1) fetch(s + 1);        // in flight during the MFMAs
+        // rows_tile.h's order: a half wave takes columns 8 g + 4 lh .. + 3 of each group g of 8
+#pragma unroll
+        for (int g = 0; g < kBK / 8; ++g) {
+            float av[FA][4], bv[PB][4];
+#pragma unroll
+            for (int a = 0; a < FA; ++a) {
+                const float4 v = *reinterpret_cast<const float4*>(
+                    stage + (wf * FA * 32 + a * 32 + lr) * kLDK + 8 * g + 4 * lh);
+                av[a][0] = v.x; av[a][1] = v.y; av[a][2] = v.z; av[a][3] = v.w;
+            }
+#pragma unroll
+            for (int b = 0; b < PB; ++b) {
+                const float4 v = *reinterpret_cast<const float4*>(
+                    stage + (BN + wp * PB * 32 + b * 32 + lr) * kLDK + 8 * g + 4 * lh);
+                bv[b][0] = v.x; bv[b][1] = v.y; bv[b][2] = v.z; bv[b][3] = v.w;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int a = 0; a < FA; ++a)
+#pragma unroll
+                    for (int b = 0; b < PB; ++b)
+                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][e], bv[b][e], acc[a][b], 0, 0, 0);
+        }
+        __syncthreads();                     // every wave has read the stage
+        if (s + 1 < s1) store();
+        __syncthreads();
+    }
+    // part[split][feature][row]: a lane's batch row is the fastest index
+#pragma unroll
+    for (int a = 0; a < FA; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = f0 + wf * FA * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+#pragma unroll
+            for (int b = 0; b < PB; ++b) {
+                const int p = p0 + wp * PB * 32 + b * 32 + lr;
+                if (i < N && p < m) part[((int64_t)split * N + i) * m + p] = acc[a][b][r];
+            }
+        }
+}
+
+// softplus with torch's threshold, then x tanh(.)
+__device__ __forceinline__ float mish(float x) {
+    const float sp = x > 20.f ? x : log1pf(expf(x));
+    return x * tanhf(sp);
+}
+
+// The sum of v over the workgroup's 256 threads: a wave's butterfly, then the four wave sums in
+// wave order.  `red` is 4 doubles of LDS that no other sum uses.
+__device__ __forceinline__ double block_sum(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// part[split][feature][row] -> part[0][feature][row] = ((p_0 + p_1) + ... + p_{S-1}) + bias, in place: a
+// thread per (feature, row), whose S loads are contiguous across the wave; kRedUnroll of them are
+// in flight before the sequential additions take them in ascending split order.
+constexpr int kRedUnroll = 16;
+__global__ void __launch_bounds__(256)
+vladenc_reduce_kernel(float* __restrict__ part, int m, int N, int nsplit, const float* __restrict__ bias) {
+    const int64_t total = (int64_t)N * m, e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const float* const p = part + e;
+    float t = p[0];
+    int s = 1;
+    for (; s + kRedUnroll <= nsplit; s += kRedUnroll) {
+        float v[kRedUnroll];
+#pragma unroll
+        for (int q = 0; q < kRedUnroll; ++q) v[q] = p[(s + q) * total];
+#pragma unroll
+        for (int q = 0; q < kRedUnroll; ++q) t += v[q];
+    }
+    for (; s < nsplit; ++s) t += p[s * total];
+    part[e] = t + bias[e / m];
+}
+
+// Workgroup = row p of the chunk's m; ysum[feature][row] from the reduction.  dst: the row's N
+// outputs; hid: its N slots of `hidden` or NULL.
+__global__ void __launch_bounds__(256)
+vladenc_finish_kernel(const float* __restrict__ ysum, int m, int N,
+                      const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int mode,
+                      float* __restrict__ dst, int64_t dst_stride, float* __restrict__ hid, int64_t hid_stride) {
+    __shared__ float y[VLADENC_MAX_WIDTH];
+    __shared__ double red[3][4];
+    const int tid = threadIdx.x, p = blockIdx.x;
+    for (int f = tid; f < N; f += 256) y[f] = ysum[(int64_t)f * m + p];
+    __syncthreads();
+    float* const o = dst + p * dst_stride;
+    if (mode == kHidden) {
+        double a = 0.0;
+        for (int f = tid; f < N; f += 256) a += (double)y[f];
+        const double mean = block_sum(a, red[0]) / N;
+        a = 0.0;
+        for (int f = tid; f < N; f += 256) {
+            const double t = (double)y[f] - mean;
+            a = fma(t, t, a);
+        }
+        const double sd = sqrt(block_sum(a, red[1]) / N + (double)eps);
+        for (int f = tid; f < N; f += 256) {
+            const float v = (float)(((double)y[f] - mean) / sd);
+            const float h = mish(fmaf(v, gamma[f], beta[f]));
+            o[f] = h;
+            if (hid) hid[p * hid_stride + f] = h;
+        }
+        return;
+    }
+    double a = 0.0;
+    for (int f = tid; f < N; f += 256) a = fma((double)y[f], (double)y[f], a);
+    const double nrm = fmax(sqrt(block_sum(a, red[0])), 1e-12);
+    a = 0.0;
+    for (int f = tid; f < N; f += 256) {       // a thread re-reads only what it wrote
+        const float u = (float)((double)y[f] / nrm);
+        y[f] = u;
+        a = fma((double)u, (double)u, a);
+    }
+    if (mode == kModelOutput) {
+        for (int f = tid; f < N; f += 256) o[f] = y[f];
+        return;
+    }
+    const double den = sqrt(block_sum(a, red[1])) + 1e-7;
+    for (int f = tid; f < N; f += 256) o[f] = (float)((double)y[f] / den);
+}
+
+// ---- host side ----------------------------------------------------------------------------------
+
+// what the calls on a device share (dev_workspace.h), whichever handle they belong to
+struct Workspace : StreamHandoff {
+    DevBuf<float> part;
+    DevBuf<float> act[2];
+};
+
+template <int FW, int PW, int FA, int PB>
+int launch_linear(const float* x, int m, int K, const float* W, int N, const EncSplit& sp, float* part,
+                  hipStream_t st) {
+    constexpr int BM = PW * PB * 32;
+    const int vec_x = K % 4 == 0 && (uintptr_t)x % 16 == 0, vec_w = K % 4 == 0 && (uintptr_t)W % 16 == 0;
+    auto* kern = vladenc_linear_kernel<FW, PW, FA, PB>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)sp.tiles, (unsigned)sp.nsplit, (unsigned)((m + BM - 1) / BM)), dim3(kNT),
+                       0, st, x, m, K, W, N, sp.per, sp.stages, vec_x, vec_w, part);
+    KNN_HIP(hipGetLastError());
+    return KNN_OK;
+}
+
+// the launches on `st` (w->mu held)
+int forward_locked(Workspace* w, const vladenc* h, const float* x, int64_t n, int flags, float* out, float* hidden,
+                   hipStream_t st) {
+    const char* e = test_knob("IMGREC_VLADENC_CHUNK_ROWS");
+    const int L = h->nlayers, chunk = (int)std::min<int64_t>(vladenc_chunk_rows(e ? std::atoll(e) : 0), n);
+    int64_t pf = 1;
+    for (int l = 0; l < L; ++l) {
+        const int K = h->widths[l], N = h->widths[l + 1];
+        pf = std::max(pf, vladenc_part_floats(K, N, vladenc_layer_rows(K, N, chunk)));
+    }
+    int rc;
+    if ((rc = w->part.reserve((size_t)pf)) != KNN_OK) return rc;
+    for (int i = 0; i < 2; ++i)
+        if ((rc = w->act[i].reserve((size_t)chunk * h->hmax)) != KNN_OK) return rc;
+    const int nout = h->widths[L];
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int M = (int)std::min<int64_t>(chunk, n - c0);
+        const float* in = x + c0 * h->widths[0];
+        int hoff = 0;
+        for (int l = 0; l < L; ++l) {
+            const int K = h->widths[l], N = h->widths[l + 1], rows = vladenc_layer_rows(K, N, chunk);
+            const EncSplit sp = vladenc_split(K, N);
+            const bool last = l == L - 1;
+            float* const dst = last ? out + c0 * nout : w->act[l & 1].get();
+            float* const hid = !last && hidden ? hidden + c0 * h->hsum + hoff : nullptr;
+            const int mode = !last ? kHidden : (flags & VLADENC_MODEL_OUTPUT) ? kModelOutput : kStored;
+            for (int r0 = 0; r0 < M; r0 += rows) {
+                const int m = std::min(rows, M - r0);
+                const float* xin = in + (int64_t)r0 * K;
+                rc = m <= 32 ? launch_linear<8, 1, 1, 1>(xin, m, K, h->W[l], N, sp, w->part, st)
+                             : launch_linear<4, 2, 2, 2>(xin, m, K, h->W[l], N, sp, w->part, st);
+                if (rc != KNN_OK) return rc;
+                hipLaunchKernelGGL(vladenc_reduce_kernel, dim3((unsigned)(((int64_t)N * m + 255) / 256)), dim3(256), 0,
+                                   st, w->part.get(), m, N, sp.nsplit, h->b[l].get());
+                KNN_HIP(hipGetLastError());
+                hipLaunchKernelGGL(vladenc_finish_kernel, dim3((unsigned)m), dim3(256), 0, st, w->part.get(), m, N,
+                                   last ? nullptr : h->g[l].get(), last ? nullptr : h->be[l].get(), h->eps, mode,
+                                   dst + (int64_t)r0 * N, (int64_t)N, hid ? hid + (int64_t)r0 * h->hsum : nullptr,
+                                   (int64_t)h->hsum);
+                KNN_HIP(hipGetLastError());
+            }
+            in = dst;
+            hoff += N;
+        }
+    }
+    return KNN_OK;
+}
+
+int check_forward(const vladenc* h, const float* x, int64_t n, int flags, const float* out, const char* who) {
+    char msg[256];
+    if (vladenc_check_forward(h, x, n, flags, out, who, msg, sizeof msg) != 0) KNN_FAIL(KNN_EINVAL, "%s", msg);
+    return KNN_OK;
+}
+
+// on the handle's device (set by the caller)
+int forward_device_impl(vladenc* h, const float* x, int64_t n, int flags, float* out, float* hidden, hipStream_t st) {
+    Workspace* w = per_device<Workspace>(h->device);
+    HandoffOp op(w);
+    int rc = op.begin(st);
+    if (rc == KNN_OK) rc = forward_locked(w, h, x, n, flags, out, hidden, st);
+    return op.finish(rc);
+}
+
+}  // namespace
+}  // namespace imgrec
+
+using namespace imgrec;
+
+extern "C" {
+
+int vladenc_create(int nlayers, const int* widths, const float* const* W, const float* const* b,
+                   const float* const* gamma, const float* const* beta, float ln_eps, int device,
+                   vladenc_t** out) {
+    char msg[256];
+    if (vladenc_check_create(nlayers, widths, W, b, gamma, beta, ln_eps, out, "vladenc_create", msg, sizeof msg) != 0)
+        KNN_FAIL(KNN_EINVAL, "%s", msg);
+    *out = nullptr;
+    int rc = have_device();
+    if (rc != KNN_OK) return rc;
+    int ndev = 0;
+    KNN_HIP(hipGetDeviceCount(&ndev));
+    if (device >= ndev) KNN_FAIL(KNN_EINVAL, "vladenc_create: device %d out of range (%d visible)", device, ndev);
+    DeviceGuard g(device);
+    vladenc* h = new vladenc();
+    struct Drop {
+        vladenc* h;
+        ~Drop() { delete h; }
+    } drop{h};
+    h->nlayers = nlayers;
+    h->eps = ln_eps;
+    KNN_HIP(hipGetDevice(&h->device));
+    for (int l = 0; l <= nlayers; ++l) h->widths[l] = widths[l];
+    for (int l = 1; l < nlayers; ++l) {
+        h->hsum += widths[l];
+        h->hmax = std::max(h->hmax, widths[l]);
+    }
+    auto upload = [](DevBuf<float>& d, const float* src, size_t count) -> int {
+        const int rc = d.reserve(count);
+        if (rc != KNN_OK) return rc;
+        KNN_HIP(hipMemcpy(d.get(), src, count * sizeof(float), hipMemcpyHostToDevice));
+        return KNN_OK;
+    };
+    for (int l = 0; l < nlayers; ++l) {
+        const size_t K = (size_t)widths[l], N = (size_t)widths[l + 1];
+        if ((rc = upload(h->W[l], W[l], N * K)) != KNN_OK) return rc;
+        if ((rc = upload(h->b[l], b[l], N)) != KNN_OK) return rc;
+        if (l < nlayers - 1) {
+            if ((rc = upload(h->g[l], gamma[l], N)) != KNN_OK) return rc;
+            if ((rc = upload(h->be[l], beta[l], N)) != KNN_OK) return rc;
+        }
+    }
+    drop.h = nullptr;
+    *out = h;
+    return KNN_OK;
+}
+
+int vladenc_free(vladenc_t* h) {
+    if (!h) return KNN_OK;
+    {
+        // calls still in flight read the weights: the device is drained before they go
+        DeviceGuard g(h->device);
+        (void)hipDeviceSynchronize();
+    }
+    delete h;
+    return KNN_OK;
+}
+
+int vladenc_widths(const vladenc_t* h, int* out, int* nlayers) {
+    if (!h) KNN_FAIL(KNN_EINVAL, "vladenc_widths: NULL handle");
+    if (out)
+        for (int l = 0; l <= h->nlayers; ++l) out[l] = h->widths[l];
+    if (nlayers) *nlayers = h->nlayers;
+    return KNN_OK;
+}
+
+int vladenc_forward_device(vladenc_t* h, const float* x, int64_t n, int flags, float* out, float* hidden,
+                           void* stream) {
+    const int rc = check_forward(h, x, n, flags, out, "vladenc_forward_device");
+    if (rc != KNN_OK || n == 0) return rc;
+    DeviceGuard g(h->device);
+    return forward_device_impl(h, x, n, flags, out, hidden, (hipStream_t)stream);
+}
+
+int vladenc_forward(vladenc_t* h, const float* x, int64_t n, int flags, float* out, float* hidden) {
+    int rc = check_forward(h, x, n, flags, out, "vladenc_forward");
+    if (rc != KNN_OK || n == 0) return rc;
+    DeviceGuard g(h->device);
+    const size_t nx = (size_t)n * h->widths[0], no = (size_t)n * h->widths[h->nlayers], nh = (size_t)n * h->hsum;
+    DevBuf<float> xd, od, hd;
+    if ((rc = xd.reserve(nx)) != KNN_OK) return rc;
+    if ((rc = od.reserve(no)) != KNN_OK) return rc;
+    const bool want_hidden = hidden && nh > 0;
+    if (want_hidden && (rc = hd.reserve(nh)) != KNN_OK) return rc;
+    StreamGuard sg;       // declared after the buffers: the stream is drained before they are freed
+    KNN_HIP(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    KNN_HIP(hipMemcpyAsync(xd, x, nx * sizeof(float), hipMemcpyHostToDevice, sg.s));
+    if ((rc = forward_device_impl(h, xd, n, flags, od, want_hidden ? hd.get() : nullptr, sg.s)) != KNN_OK) return rc;
+    KNN_HIP(hipMemcpyAsync(out, od, no * sizeof(float), hipMemcpyDeviceToHost, sg.s));
+    if (want_hidden) KNN_HIP(hipMemcpyAsync(hidden, hd, nh * sizeof(float), hipMemcpyDeviceToHost, sg.s));
+    KNN_HIP(hipStreamSynchronize(sg.s));
+    return KNN_OK;
+}
+
+}  // extern "C"

@@ -132,9 +132,10 @@ class ImageRecommender:
 
     def extract_sift_vlad_features(self, path_rel: str):
         def compute():
-            logging.error("SIFT-VLAD extraction needs the trained codebook/encoder of the "
-                          "reference's vector_scripts/create_sift_vector.py; only DB-cached "
-                          "SIFT vectors are served by this search path.")
+            logging.error("No cached SIFT vector, and SIFT keypoint detection (OpenCV) is not part of "
+                          "this package: given an image's descriptors, vlad.SoftVLAD (sift_codebook.npy) "
+                          "and vlad_encoder.VladEncoder (sift_vlad_encoder.pt) produce the stored vector; "
+                          "this search path serves only DB-cached SIFT vectors.")
             return None
         return self.get_or_compute_vector(path_rel, "sift_vectors", "sift_vector_blob", compute)
 

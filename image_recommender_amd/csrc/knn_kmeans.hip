@@ -133,8 +133,7 @@ kmeans_assign_kernel(const float* __restrict__ x, int64_t n, int d, const float*
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sum[q] += __shfl_xor(sum[q], o);
+            sum[q] = wave_sum(sum[q]);
             const int pl = wave * PW + pp + q;
             const bool live = p0 + pl < n;
             if (lane == 0) {
@@ -274,8 +273,7 @@ kmeans_normalize_kernel(float* __restrict__ c, int k, int d) {
     float* p = c + (int64_t)row * d;
     float s = 0.f;
     for (int j = lane; j < d; j += 64) s = fmaf(p[j], p[j], s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum(s);
     if (s > 0.f) {
         const float inv = 1.f / sqrtf(s);
         for (int j = lane; j < d; j += 64) p[j] *= inv;
@@ -313,8 +311,7 @@ int check_step_args(const void* x, int64_t n, int d, const void* c, int k, const
                              "of clusters (%d)", who, (long long)n, k);
     if (n >= (int64_t(1) << 31)) KNN_FAIL(KNN_EINVAL, "%s: n = %lld rows (limit 2^31 - 1)", who, (long long)n);
     if (!x || !c) KNN_FAIL(KNN_EINVAL, "%s: NULL points or centroids", who);
-    const int64_t stages = ((int64_t)k + kBN - 1) / kBN * (((int64_t)d + kBK - 1) / kBK);
-    if (stages >= (int64_t(1) << 31)) KNN_FAIL(KNN_EINVAL, "%s: k x d too large (%d x %d)", who, k, d);
+    if (!row_stages_fit(k, d)) KNN_FAIL(KNN_EINVAL, "%s: k x d too large (%d x %d)", who, k, d);
     return KNN_OK;
 }
 
@@ -355,9 +352,8 @@ int step_locked(Workspace* w, const float* x, int64_t n, int d, const float* c, 
     if (ev) KNN_HIP(hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(kmeans_norms_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, c, k, d, w->cnorm);
     KNN_HIP(hipGetLastError());
-    const int vec_x = d % 4 == 0 && (uintptr_t)x % 16 == 0, vec_c = d % 4 == 0 && (uintptr_t)c % 16 == 0;
     hipLaunchKernelGGL(kmeans_assign_kernel, dim3((unsigned)nblk), dim3(kNT), 0, st, x, n, d, c, w->cnorm, k,
-                       (flags & KMEANS_SPHERICAL) ? 1 : 0, vec_x, vec_c, assign, dist, w->partial);
+                       (flags & KMEANS_SPHERICAL) ? 1 : 0, row4_vec(x, d), row4_vec(c, d), assign, dist, w->partial);
     KNN_HIP(hipGetLastError());
     hipLaunchKernelGGL(kmeans_obj_kernel, dim3(1), dim3(256), 0, st, w->partial, nblk, obj);
     KNN_HIP(hipGetLastError());
@@ -449,9 +445,6 @@ struct Events {
 int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_params_t* prm, const float* init,
                       float* cout_, double* obj_out, double* stats_out, hipStream_t st) {
     using clk = std::chrono::steady_clock;
-    int device = 0;
-    KNN_HIP(hipGetDevice(&device));
-    Workspace* w = per_device<Workspace>(device);
     const size_t kd = (size_t)k * d;
     DevBuf<float> ca, cb, di;
     DevBuf<int32_t> as;
@@ -476,10 +469,7 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
     for (int redo = 0; redo < prm->nredo; ++redo) {
         float* cur = ca;
         float* nxt = cb;
-        {
-            HandoffOp op(w);
-            int rc = op.begin(st);
-            if (rc != KNN_OK) return rc;
+        rc = on_workspace<Workspace>(st, [&](Workspace*) -> int {
             if (init) {
                 KNN_HIP(hipMemcpyAsync(cur, init, kd * sizeof(float), hipMemcpyHostToDevice, st));
             } else {
@@ -503,25 +493,22 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
                 hipLaunchKernelGGL(kmeans_normalize_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, cur, k, d);
                 KNN_HIP(hipGetLastError());
             }
-            if ((rc = op.finish(KNN_OK)) != KNN_OK) return rc;
-        }
+            return KNN_OK;
+        });
+        if (rc != KNN_OK) return rc;
         const clk::time_point t0 = clk::now();
         double t_search = 0.0, obj = 0.0;
         for (int it = 0; it < prm->niter; ++it) {
             const clk::time_point ts = clk::now();
             int nsplit = 0;
-            {
-                HandoffOp op(w);
-                int rc = op.begin(st);
+            double s1 = 0.0, s2 = 0.0;
+            rc = on_workspace<Workspace>(st, [&](Workspace* w) -> int {
+                int rc = step_locked(w, x, n, d, cur, k, flags, as, di, nxt, cnt_d, obj_d, st, evs.e);
                 if (rc != KNN_OK) return rc;
-                if ((rc = step_locked(w, x, n, d, cur, k, flags, as, di, nxt, cnt_d, obj_d,
-                                      st, evs.e)) != KNN_OK)
-                    return rc;
                 KNN_HIP(hipMemcpyAsync(host.data(), cnt_d, ((size_t)k + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
                 KNN_HIP(hipStreamSynchronize(st));
                 t_search += std::chrono::duration<double>(clk::now() - ts).count();
                 std::memcpy(&obj, &host[k], sizeof(double));
-                double s1 = 0.0, s2 = 0.0;
                 for (int c = 0; c < k; ++c) {
                     s1 += (double)host[c];
                     s2 += (double)host[c] * (double)host[c];
@@ -531,17 +518,18 @@ int train_device_impl(const float* x, int64_t n, int d, int k, const kmeans_para
                     hipLaunchKernelGGL(kmeans_normalize_kernel, dim3((unsigned)((k + 3) / 4)), dim3(256), 0, st, nxt, k, d);
                     KNN_HIP(hipGetLastError());
                 }
-                if ((rc = op.finish(KNN_OK)) != KNN_OK) return rc;
-                float ms[3] = {0.f, 0.f, 0.f};
-                for (int e = 0; e < 3; ++e) KNN_HIP(hipEventElapsedTime(&ms[e], evs.e[e], evs.e[e + 1]));
-                double* s = &stats[(size_t)it * KMEANS_STATS_PER_ITER];
-                s[0] = obj;
-                s[1] = std::chrono::duration<double>(clk::now() - t0).count();
-                s[2] = t_search;
-                s[3] = s1 > 0.0 ? (double)k * s2 / (s1 * s1) : 0.0;
-                s[4] = (double)nsplit;
-                s[5] = ms[0]; s[6] = ms[1]; s[7] = ms[2];
-            }
+                return KNN_OK;
+            });
+            if (rc != KNN_OK) return rc;
+            float ms[3] = {0.f, 0.f, 0.f};
+            for (int e = 0; e < 3; ++e) KNN_HIP(hipEventElapsedTime(&ms[e], evs.e[e], evs.e[e + 1]));
+            double* s = &stats[(size_t)it * KMEANS_STATS_PER_ITER];
+            s[0] = obj;
+            s[1] = std::chrono::duration<double>(clk::now() - t0).count();
+            s[2] = t_search;
+            s[3] = s1 > 0.0 ? (double)k * s2 / (s1 * s1) : 0.0;
+            s[4] = (double)nsplit;
+            s[5] = ms[0]; s[6] = ms[1]; s[7] = ms[2];
             if (prm->verbose)
                 std::fprintf(stderr, "  Iteration %d (%.2f s, search %.2f s): objective=%g imbalance=%.3f nsplit=%d\n",
                              it, stats[(size_t)it * KMEANS_STATS_PER_ITER + 1], t_search, obj,
@@ -584,14 +572,10 @@ int kmeans_step_device(const float* x, int64_t n, int d, const float* centroids,
     if (new_centroids == centroids) KNN_FAIL(KNN_EINVAL, "kmeans_step_device: new_centroids aliases centroids");
     if (flags & ~KMEANS_SPHERICAL) KNN_FAIL(KNN_EINVAL, "kmeans_step_device: unknown flags 0x%x", flags);
     if ((rc = have_device()) != KNN_OK) return rc;
-    int device = 0;
-    KNN_HIP(hipGetDevice(&device));
-    Workspace* w = per_device<Workspace>(device);
     hipStream_t st = (hipStream_t)stream;
-    HandoffOp op(w);
-    if ((rc = op.begin(st)) == KNN_OK)
-        rc = step_locked(w, x, n, d, centroids, k, flags, assign, dist, new_centroids, counts, obj, st, nullptr);
-    return op.finish(rc);
+    return on_workspace<Workspace>(st, [&](Workspace* w) {
+        return step_locked(w, x, n, d, centroids, k, flags, assign, dist, new_centroids, counts, obj, st, nullptr);
+    });
 }
 
 int kmeans_split_device(float* centroids, int k, int d, int64_t* counts_host, int* nsplit, void* stream) {
@@ -608,13 +592,9 @@ int kmeans_split_device(float* centroids, int k, int d, int64_t* counts_host, in
         if (pairs.empty()) return KNN_OK;
     }
     if ((rc = have_device()) != KNN_OK) return rc;
-    int device = 0;
-    KNN_HIP(hipGetDevice(&device));
-    Workspace* w = per_device<Workspace>(device);
     hipStream_t st = (hipStream_t)stream;
-    HandoffOp op(w);
-    if ((rc = op.begin(st)) == KNN_OK) rc = split_locked(w, centroids, k, d, counts_host, nsplit, st);
-    return op.finish(rc);
+    return on_workspace<Workspace>(
+        st, [&](Workspace* w) { return split_locked(w, centroids, k, d, counts_host, nsplit, st); });
 }
 
 int kmeans_train_device(const float* x_dev, int64_t n, int d, int k, const kmeans_params_t* params,

@@ -189,8 +189,7 @@ vlad_nn_kernel(const float* __restrict__ x, int64_t n, int d, const float* __res
         }
 #pragma unroll
         for (int q = 0; q < kDP; ++q) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sum[q] += __shfl_xor(sum[q], o);
+            sum[q] = wave_sum(sum[q]);
             if (lane == 0 && p0 + pl[q] < n) {
                 const int64_t o = (p0 + pl[q]) * nn + sl[q];
                 nn_idx[o] = id[q];
@@ -290,11 +289,8 @@ vlad_epilogue_kernel(float* __restrict__ out, int k, int d, double* __restrict__
             s = fma(t, t, s);
             a += fabs(t);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            s += __shfl_xor(s, o);
-            a += __shfl_xor(a, o);
-        }
+        s = wave_sum(s);
+        a = wave_sum(a);
         if (lane == 0) {
             const double r = sqrt(s);
             rn[row] = r;
@@ -353,9 +349,8 @@ int64_t acc_floats() {
 template <int L>
 int launch_nn(const float* x, int64_t n, int d, const float* c, const float* cn, int k, int nn, int32_t* idx,
               float* dist, hipStream_t st) {
-    const int vec_x = d % 4 == 0 && (uintptr_t)x % 16 == 0, vec_c = d % 4 == 0 && (uintptr_t)c % 16 == 0;
     hipLaunchKernelGGL(vlad_nn_kernel<L>, dim3((unsigned)((n + kBM - 1) / kBM)), dim3(kNT), 0, st, x, n, d, c, cn,
-                       k, nn, vec_x, vec_c, idx, dist);
+                       k, nn, row4_vec(x, d), row4_vec(c, d), idx, dist);
     KNN_HIP(hipGetLastError());
     return KNN_OK;
 }
@@ -412,12 +407,8 @@ int encode_device_impl(const VladArgs& a, int32_t* nn_idx, float* nn_dist, hipSt
         KNN_FAIL(KNN_EINVAL, "%s", msg);
     int rc = have_device();
     if (rc != KNN_OK) return rc;
-    int device = 0;
-    KNN_HIP(hipGetDevice(&device));
-    Workspace* w = per_device<Workspace>(device);
-    HandoffOp op(w);
-    if ((rc = op.begin(st)) == KNN_OK) rc = encode_locked(w, a, ct, ntiles, nn_idx, nn_dist, st);
-    return op.finish(rc);
+    return on_workspace<Workspace>(
+        st, [&](Workspace* w) { return encode_locked(w, a, ct, ntiles, nn_idx, nn_dist, st); });
 }
 
 }  // namespace

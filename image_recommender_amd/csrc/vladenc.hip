@@ -4,11 +4,12 @@
 // A batch runs in chunks of VLADENC_SUPER_ROWS rows; inside a chunk a layer is three launches on the
 // caller's stream per group of row tiles (as many as keep the partial sums within 64 MiB: one tile
 // of 128 rows for the reference's first layer, the whole chunk for its later layers):
-//   1. vladenc_linear_kernel<..>  grid = feature tiles (256) x depth splits x row tiles.  The tile of
-//                                 rows_tile.h turned to a plain GEMM: the weight rows are the MFMA's A
-//                                 rows, the batch rows its columns, 32 depth columns per stage through
-//                                 LDS (row stride kLDK, load_row4's guarded loads for ragged K, N and
-//                                 batch), the next stage's global loads in registers during the MFMAs.
+//   1. vladenc_linear_kernel<..>  grid = feature tiles (256) x depth splits x row tiles.  A plain GEMM
+//                                 on rows_tile.h's stage_stream, the loop kmeans_assign_kernel and
+//                                 vlad_nn_kernel run: the weight rows are the MFMA's A rows, the batch
+//                                 rows its columns, 32 depth columns per stage (load_row4's guarded
+//                                 loads for ragged K, N and batch).  The kernel itself is the index
+//                                 arithmetic, the stage's load and the epilogue.
 //                                 A workgroup streams only its split's stages and leaves its
 //                                 accumulators, one fmaf chain per (row, feature), in the workspace as
 //                                 part[split][feature][row]: a lane owns a batch row, so a register's
@@ -59,12 +60,10 @@ struct vladenc {
 namespace imgrec {
 namespace {
 
-static_assert(kEncStage == kBK && kEncFeat == kBN, "the split rule counts this tile's stages and feature tiles");
-
 enum { kHidden = 0, kModelOutput = 1, kStored = 2 };     // what the finish kernel does after the bias
 
-// Waves per SIMD the 128-row shape is compiled for.  4 = two workgroups per CU: 128 VGPRs with 14 of
-// its 158 spilled to scratch, and still 6 % faster at B = 1024 than one workgroup per CU
+// Waves per SIMD the 128-row shape is compiled for.  4 = two workgroups per CU: 128 VGPRs with 12
+// of its 160 spilled to scratch, and still 6 % faster at B = 1024 than one workgroup per CU
 // (-DVLADENC_WIDE_WAVES=1; profiles/vladenc/), because a neighbour's MFMAs cover a workgroup's
 // first load, barriers and stores.
 #ifndef VLADENC_WIDE_WAVES
@@ -76,83 +75,30 @@ template <int FW, int PW, int FA, int PB>
 __global__ void __launch_bounds__(kNT, FA * PB == 4 ? VLADENC_WIDE_WAVES : 1)
 vladenc_linear_kernel(const float* __restrict__ x, int m, int K, const float* __restrict__ W, int N, int per,
                       int stages, int vec_x, int vec_w, float* __restrict__ part) {
-    constexpr int BN = FW * FA * 32, BM = PW * PB * 32, R = BN + BM, LD4 = (R * kQ + kNT - 1) / kNT;
-    static_assert(FW * PW * 64 == kNT && BN == kBN, "eight waves, one feature tile");
-    __shared__ __attribute__((aligned(16))) float stage[R * kLDK];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
-    const int wf = wave % FW, wp = wave / FW;
-    const int f0 = blockIdx.x * BN, split = blockIdx.y, p0 = blockIdx.z * BM;
+    using G = StageGeom<FW, PW, FA, PB>;
+    static_assert(G::BN == kBN, "one feature tile of the split rule");
+    __shared__ __attribute__((aligned(16))) float stage[G::R * kLDK];
+    const int f0 = blockIdx.x * G::BN, split = blockIdx.y, p0 = blockIdx.z * G::BM;
     const int s0 = split * per, s1 = min(s0 + per, stages);
 
-    float4 pre[LD4];
-    auto fetch = [&](int s) __attribute__((always_inline)) {
-#pragma unroll
-        for (int it = 0; it < LD4; ++it) {
-            const int idx = tid + it * kNT, row = idx / kQ, col = s * kBK + 4 * (idx % kQ);
-            if (R * kQ % kNT == 0 || idx < R * kQ)
-                pre[it] = row < BN ? load_row4(W, (int64_t)f0 + row, N, K, col, vec_w)
-                                   : load_row4(x, (int64_t)p0 + (row - BN), m, K, col, vec_x);
-        }
-    };
-    auto store = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int it = 0; it < LD4; ++it) {
-            const int idx = tid + it * kNT;
-            if (R * kQ % kNT == 0 || idx < R * kQ)
-                *reinterpret_cast<float4*>(stage + (idx / kQ) * kLDK + 4 * (idx % kQ)) = pre[it];
-        }
-    };
-
     f32x16 acc[FA][PB];
-#pragma unroll
-    for (int a = 0; a < FA; ++a)
-#pragma unroll
-        for (int b = 0; b < PB; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    fetch(s0);
-    store();
-    __syncthreads();
-    for (int s = s0; s < s1; ++s) {
-        if (s + 1 < s1) fetch(s + 1);        // in flight during the MFMAs
-        // rows_tile.h's order: a half wave takes columns 8 g + 4 lh .. + 3 of each group g of 8
-#pragma unroll
-        for (int g = 0; g < kBK / 8; ++g) {
-            float av[FA][4], bv[PB][4];
-#pragma unroll
-            for (int a = 0; a < FA; ++a) {
-                const float4 v = *reinterpret_cast<const float4*>(
-                    stage + (wf * FA * 32 + a * 32 + lr) * kLDK + 8 * g + 4 * lh);
-                av[a][0] = v.x; av[a][1] = v.y; av[a][2] = v.z; av[a][3] = v.w;
-            }
-#pragma unroll
-            for (int b = 0; b < PB; ++b) {
-                const float4 v = *reinterpret_cast<const float4*>(
-                    stage + (BN + wp * PB * 32 + b * 32 + lr) * kLDK + 8 * g + 4 * lh);
-                bv[b][0] = v.x; bv[b][1] = v.y; bv[b][2] = v.z; bv[b][3] = v.w;
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int a = 0; a < FA; ++a)
-#pragma unroll
-                    for (int b = 0; b < PB; ++b)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a][e], bv[b][e], acc[a][b], 0, 0, 0);
-        }
-        __syncthreads();                     // every wave has read the stage
-        if (s + 1 < s1) store();
-        __syncthreads();
-    }
+    stage_stream<G>(
+        stage, s0, s1, acc,
+        [&](int s, int row, int c4) __attribute__((always_inline)) {
+            return row < G::BN ? load_row4(W, (int64_t)f0 + row, N, K, s * kBK + c4, vec_w)
+                               : load_row4(x, (int64_t)p0 + (row - G::BN), m, K, s * kBK + c4, vec_x);
+        },
+        [](int) {}, [](int) {});
     // part[split][feature][row]: a lane's batch row is the fastest index
+    const StageLanes<G> t;
 #pragma unroll
     for (int a = 0; a < FA; ++a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int i = f0 + wf * FA * 32 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int i = f0 + t.acc_row(a, r);
 #pragma unroll
             for (int b = 0; b < PB; ++b) {
-                const int p = p0 + wp * PB * 32 + b * 32 + lr;
+                const int p = p0 + t.acc_point(b);
                 if (i < N && p < m) part[((int64_t)split * N + i) * m + p] = acc[a][b][r];
             }
         }
@@ -167,8 +113,7 @@ __device__ __forceinline__ float mish(float x) {
 // The sum of v over the workgroup's 256 threads: a wave's butterfly, then the four wave sums in
 // wave order.  `red` is 4 doubles of LDS that no other sum uses.
 __device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return ((red[0] + red[1]) + red[2]) + red[3];
@@ -255,10 +200,9 @@ template <int FW, int PW, int FA, int PB>
 int launch_linear(const float* x, int m, int K, const float* W, int N, const EncSplit& sp, float* part,
                   hipStream_t st) {
     constexpr int BM = PW * PB * 32;
-    const int vec_x = K % 4 == 0 && (uintptr_t)x % 16 == 0, vec_w = K % 4 == 0 && (uintptr_t)W % 16 == 0;
     auto* kern = vladenc_linear_kernel<FW, PW, FA, PB>;
     hipLaunchKernelGGL(kern, dim3((unsigned)sp.tiles, (unsigned)sp.nsplit, (unsigned)((m + BM - 1) / BM)), dim3(kNT),
-                       0, st, x, m, K, W, N, sp.per, sp.stages, vec_x, vec_w, part);
+                       0, st, x, m, K, W, N, sp.per, sp.stages, row4_vec(x, K), row4_vec(W, K), part);
     KNN_HIP(hipGetLastError());
     return KNN_OK;
 }
@@ -319,11 +263,8 @@ int check_forward(const vladenc* h, const float* x, int64_t n, int flags, const 
 
 // on the handle's device (set by the caller)
 int forward_device_impl(vladenc* h, const float* x, int64_t n, int flags, float* out, float* hidden, hipStream_t st) {
-    Workspace* w = per_device<Workspace>(h->device);
-    HandoffOp op(w);
-    int rc = op.begin(st);
-    if (rc == KNN_OK) rc = forward_locked(w, h, x, n, flags, out, hidden, st);
-    return op.finish(rc);
+    return on_workspace<Workspace>(
+        st, [&](Workspace* w) { return forward_locked(w, h, x, n, flags, out, hidden, st); });
 }
 
 }  // namespace

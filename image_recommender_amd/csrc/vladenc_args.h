@@ -9,63 +9,57 @@
 #include <cstdio>
 
 #include "../../include/imgrec_vladenc.h"
+#include "rows_geom.h"
 
 namespace imgrec {
 
-constexpr int kEncStage = 32;          // depth columns per stage (rows_tile.h kBK)
-constexpr int kEncFeat = 256;          // features per workgroup (rows_tile.h kBN)
+// a workgroup takes kBN features (a row tile) and streams stages of kBK depth columns (rows_geom.h)
 constexpr int kEncTargetWgs = 512;     // feature tiles x splits aimed at: two workgroups per CU
 constexpr int kEncMinStages = 4;       // a split is at least this deep (but for a short layer)
 // the most partial sums a launch leaves, whatever the layer (vladenc_split: tiles x splits <= 512)
-constexpr int64_t kEncMaxPartFloats = (int64_t)VLADENC_CHUNK_ROWS * kEncTargetWgs * kEncFeat;
-
-#define VLADENC_BAD(...)                      \
-    do {                                      \
-        std::snprintf(msg, cap, __VA_ARGS__); \
-        return -1;                            \
-    } while (0)
+constexpr int64_t kEncMaxPartFloats = (int64_t)VLADENC_CHUNK_ROWS * kEncTargetWgs * kBN;
 
 inline int vladenc_check_create(int nlayers, const int* widths, const float* const* W, const float* const* b,
                                 const float* const* gamma, const float* const* beta, float ln_eps,
                                 const void* out, const char* who, char* msg, size_t cap) {
     if (nlayers < 1 || nlayers > VLADENC_MAX_LAYERS)
-        VLADENC_BAD("%s: nlayers must be in [1, %d] (got %d)", who, VLADENC_MAX_LAYERS, nlayers);
+        ARGS_BAD("%s: nlayers must be in [1, %d] (got %d)", who, VLADENC_MAX_LAYERS, nlayers);
     if (!widths || !W || !b || !out || (nlayers > 1 && (!gamma || !beta)))
-        VLADENC_BAD("%s: NULL widths, W, b, gamma, beta or handle pointer", who);
+        ARGS_BAD("%s: NULL widths, W, b, gamma, beta or handle pointer", who);
     for (int l = 0; l <= nlayers; ++l) {
         const int lim = l == 0 ? VLADENC_MAX_IN : VLADENC_MAX_WIDTH;
         if (widths[l] < 1 || widths[l] > lim)
-            VLADENC_BAD("%s: widths[%d] must be in [1, %d] (got %d)", who, l, lim, widths[l]);
+            ARGS_BAD("%s: widths[%d] must be in [1, %d] (got %d)", who, l, lim, widths[l]);
     }
     for (int l = 0; l < nlayers; ++l) {
-        if (!W[l] || !b[l]) VLADENC_BAD("%s: NULL weight or bias of layer %d", who, l);
-        if (l < nlayers - 1 && (!gamma[l] || !beta[l])) VLADENC_BAD("%s: NULL LayerNorm weight or bias of layer %d", who, l);
+        if (!W[l] || !b[l]) ARGS_BAD("%s: NULL weight or bias of layer %d", who, l);
+        if (l < nlayers - 1 && (!gamma[l] || !beta[l])) ARGS_BAD("%s: NULL LayerNorm weight or bias of layer %d", who, l);
     }
-    if (!(ln_eps >= 0.f) || !(ln_eps <= 1e18f)) VLADENC_BAD("%s: ln_eps must be finite and >= 0 (got %g)", who, (double)ln_eps);
+    if (!(ln_eps >= 0.f) || !(ln_eps <= 1e18f)) ARGS_BAD("%s: ln_eps must be finite and >= 0 (got %g)", who, (double)ln_eps);
     return 0;
 }
 
 inline int vladenc_check_forward(const void* h, const void* x, int64_t n, int flags, const void* out,
                                  const char* who, char* msg, size_t cap) {
-    if (!h) VLADENC_BAD("%s: NULL handle", who);
-    if (flags & ~VLADENC_MODEL_OUTPUT) VLADENC_BAD("%s: unknown flags 0x%x", who, flags);
-    if (n < 0 || n >= (int64_t(1) << 31)) VLADENC_BAD("%s: n = %lld rows (limit 2^31 - 1)", who, (long long)n);
-    if (n > 0 && (!x || !out)) VLADENC_BAD("%s: NULL x or out", who);
+    if (!h) ARGS_BAD("%s: NULL handle", who);
+    if (flags & ~VLADENC_MODEL_OUTPUT) ARGS_BAD("%s: unknown flags 0x%x", who, flags);
+    if (n < 0 || n >= (int64_t(1) << 31)) ARGS_BAD("%s: n = %lld rows (limit 2^31 - 1)", who, (long long)n);
+    if (n > 0 && (!x || !out)) ARGS_BAD("%s: NULL x or out", who);
     return 0;
 }
 
 // How a layer of depth K and N features is cut (imgrec_vladenc.h "linear"): a function of (K, N) only.
 struct EncSplit {
-    int tiles;     // feature tiles of kEncFeat
-    int stages;    // stages of kEncStage columns
+    int tiles;     // feature tiles of kBN
+    int stages;    // stages of kBK columns
     int per;       // stages per split
     int nsplit;    // splits: split s = stages [s * per, min((s + 1) * per, stages))
 };
 
 inline EncSplit vladenc_split(int K, int N) {
     EncSplit s;
-    s.tiles = (N + kEncFeat - 1) / kEncFeat;
-    s.stages = (K + kEncStage - 1) / kEncStage;
+    s.tiles = (N + kBN - 1) / kBN;
+    s.stages = (K + kBK - 1) / kBK;
     const int want = kEncTargetWgs / s.tiles > 1 ? kEncTargetWgs / s.tiles : 1;
     const int cap = s.stages / kEncMinStages > 1 ? s.stages / kEncMinStages : 1;
     const int s0 = want < cap ? want : cap;
@@ -91,7 +85,5 @@ inline int vladenc_layer_rows(int K, int N, int chunk) {
     if (rows < VLADENC_CHUNK_ROWS) rows = VLADENC_CHUNK_ROWS;
     return (int)(rows < chunk ? rows : chunk);
 }
-
-#undef VLADENC_BAD
 
 }  // namespace imgrec

@@ -68,17 +68,17 @@ static void check_split(int K, int N) {
     const EncSplit s = vladenc_split(K, N);
     const EncSplit again = vladenc_split(K, N);
     EXPECT(s.tiles == again.tiles && s.stages == again.stages && s.per == again.per && s.nsplit == again.nsplit);
-    EXPECT(s.tiles >= 1 && (int64_t)s.tiles * kEncFeat >= N && (int64_t)(s.tiles - 1) * kEncFeat < N);
-    EXPECT(s.stages >= 1 && (int64_t)s.stages * kEncStage >= K && (int64_t)(s.stages - 1) * kEncStage < K);
+    EXPECT(s.tiles >= 1 && (int64_t)s.tiles * kBN >= N && (int64_t)(s.tiles - 1) * kBN < N);
+    EXPECT(s.stages >= 1 && (int64_t)s.stages * kBK >= K && (int64_t)(s.stages - 1) * kBK < K);
     EXPECT(s.per >= 1 && s.nsplit >= 1 && s.nsplit <= 65535);
     int64_t next = 0;                                    // the first depth column not yet covered
     for (int i = 0; i < s.nsplit; ++i) {
         const int64_t s0 = (int64_t)i * s.per, s1 = s0 + s.per < s.stages ? s0 + s.per : s.stages;
         EXPECT(s0 < s1);                                 // no empty split
-        EXPECT(s0 * kEncStage == next);
-        next = s1 * kEncStage;
+        EXPECT(s0 * kBK == next);
+        next = s1 * kBK;
     }
-    EXPECT(next >= K && next - kEncStage < K);
+    EXPECT(next >= K && next - kBK < K);
     EXPECT((int64_t)s.tiles * s.nsplit <= kEncTargetWgs || s.nsplit == 1);
     // the workspace bound, for every chunk the knob can ask for, whatever n: a layer's rows per
     // launch are whole row tiles (or the chunk) and their partial sums fit

@@ -33,12 +33,23 @@ VLADENC_MAX_WIDTH = 4096
 VLADENC_MAX_IN = 1 << 20
 VLADENC_CHUNK_ROWS = 128
 VLADENC_SUPER_ROWS = 2048
+VLADTRAIN_MAX_BATCH = 4096    # include/imgrec_vladtrain.h
+VLADTRAIN_MAX_BATCH_FLOATS = 1 << 28
+VLADTRAIN_PARAMS, VLADTRAIN_ADAM_M, VLADTRAIN_ADAM_V, VLADTRAIN_GRADS = 0, 1, 2, 3
 
 
 class KmeansParams(C.Structure):
     """kmeans_params_t of include/imgrec_kmeans.h."""
     _fields_ = [("niter", C.c_int), ("nredo", C.c_int), ("spherical", C.c_int), ("verbose", C.c_int),
                 ("seed", C.c_int64), ("device", C.c_int)]
+
+class VladTrainConfig(C.Structure):
+    """vladtrain_config of include/imgrec_vladtrain.h."""
+    _fields_ = [("dropout", C.c_double), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("adam_eps", C.c_double), ("weight_decay", C.c_double), ("corr_weight", C.c_double),
+                ("umap_weight", C.c_double), ("temperature", C.c_double), ("ln_eps", C.c_double),
+                ("seed", C.c_uint64)]
+
 
 # (name, restype, argtypes) of every exported symbol — also the list the CPU test checks against
 # the headers.
@@ -112,6 +123,23 @@ SIGNATURES = {
     "vladenc_widths": (_i, [_vp, _pi, _pi]),
     "vladenc_forward_device": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "vladenc_forward": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    # imgrec_vladtrain.h
+    "vladtrain_default_config": (_i, [C.POINTER(VladTrainConfig)]),
+    "vladtrain_create": (_i, [_i, _pi, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                              C.POINTER(VladTrainConfig), _i, C.POINTER(_vp)]),
+    "vladtrain_free": (_i, [_vp]),
+    "vladtrain_step_device": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "vladtrain_step": (_i, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "vladtrain_grads_device": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "vladtrain_grads": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "vladtrain_eval_device": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "vladtrain_eval": (_i, [_vp, _vp, _i64, _vp, _i64, _vp]),
+    "vladtrain_get_state": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "vladtrain_set_state": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "vladtrain_get_step": (_i, [_vp, _pi64]),
+    "vladtrain_set_step": (_i, [_vp, _i64]),
+    "vladtrain_product_device": (_i, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "vladtrain_workspace_bytes": (_i64, [_i, _pi, _i64]),
     # imgrec_color.h
     "color_hist_device": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "color_hist_host": (_i, [_vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _vp]),

@@ -5,7 +5,7 @@ The reference pushes every image's 32768-d VLAD vector through ``SIFTVLADEncoder
 Linear(669, 317) -> LayerNorm -> Mish -> Linear(317, 128)``, then ``F.normalize``), and
 ``compute_vectors`` (``:514-521``) divides the result once more by its norm + 1e-7: that 128-d vector
 is what it stores in ``sift_vectors`` and searches.  ``VladEncoder`` runs that forward pass in HIP
-kernels (fp32 throughout, batch-invariant byte for byte); training stays in torch.
+kernels (fp32 throughout, batch-invariant byte for byte); ``vlad_trainer.VladEncoderTrainer`` trains it.
 
     vlad = SoftVLAD(np.load("sift_codebook.npy"))
     enc = VladEncoder.load("sift_vlad_encoder.pt")
@@ -18,7 +18,7 @@ reference                                        here
 ``encoder_model(X)`` (eval, no_grad)             ``forward(X, model_output=True)``
 ``compressed /= norm + 1e-7`` (stored vector)    ``forward(X)`` (the default)
 VLAD on CPU workers, then ``.to(device)``        ``encode_images(vlad, descs)``: all on the device
-``encoder_model.train()`` / the losses           not provided: training stays in torch
+``encoder_model.train()`` / the losses           ``vlad_trainer.VladEncoderTrainer`` (HIP kernels too)
 ===============================================  =====================================================
 
 There is no NumPy fallback: without the native library every call raises.

@@ -6,7 +6,7 @@
  *     Linear(32768, 669) -> LayerNorm -> Mish -> Linear(669, 317) -> LayerNorm -> Mish -> Linear(317, 128),
  * then F.normalize, and compute_vectors (:514-521) divides the result once more by its norm + 1e-7;
  * that 128-d vector is what it stores and searches.  image_recommender_amd.vlad_encoder serves the
- * forward pass from the entry points below (csrc/vladenc.hip).  Training stays in torch.
+ * forward pass from the entry points below (csrc/vladenc.hip).  Training: imgrec_vladtrain.h.
  *
  * Conventions: those of imgrec_knn.h / imgrec_vlad.h.  Every function returns 0 or a negative KNN_E*
  * code (imgrec_knn.h enum knn_error) and leaves its message in knn_last_error(); streams are

@@ -75,6 +75,10 @@ int corpus_columns(knn_index* ix, Column<DeviceSpace>* cols, bool all) {
     if (all || ix->x8) cols[n++] = {&ix->x8, (size_t)i8_row_bytes(ix->nblk8)};
     if (all || ix->x8) cols[n++] = {&ix->x8s, (size_t)ix->nblk8 * sizeof(float)};
     if (all || ix->x8) cols[n++] = {&ix->x8r, sizeof(float)};
+    // the int8 tail copy exists only once a large-batch search has materialised it (ensure_i8tail)
+    if (all || ix->xt) cols[n++] = {&ix->xt, (size_t)ix->xt_dpt};
+    if (all || ix->xt) cols[n++] = {&ix->xts, sizeof(float)};
+    if (all || ix->xt) cols[n++] = {&ix->xtm, sizeof(float4)};
     return n;
 }
 
@@ -85,28 +89,41 @@ int reserve_rows(knn_index* ix, int64_t need, hipStream_t st) {
     if (need <= ix->cap) return KNN_OK;
     const int64_t ncap = round_up(std::max(need, ix->cap + ix->cap / 2), kTileRowsMax);
     Column<DeviceSpace> live[kCorpusColumns];
-    const int n = corpus_columns(ix, live);
+    const int n_all = corpus_columns(ix, live);
+    // regrow_columns takes at most 8 columns: the int8 tail copy's three (the table's last) regrow
+    // as a group of their own after the others.  Should that second group fail, the copy — which
+    // can be rebuilt from the fp32 rows — is dropped instead of the whole regrowth.
+    const int n_tail = ix->xt ? 3 : 0, n = n_all - n_tail;
     const size_t old = (size_t)ix->ntotal;
     hipError_t e = hipSuccess;
-    const int rc = regrow_columns(
-        live, n, (size_t)ncap,
-        [&](int i, void* dst, const void* src) {
-            const size_t row = live[i].stride;
-            if (old && src) e = hipMemcpyAsync(dst, src, old * row, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipMemsetAsync((char*)dst + old * row, 0, ((size_t)ncap - old) * row, st);
-            return e == hipSuccess ? KNN_OK : KNN_EHIP;
-        },
-        [&]() {
-            const hipError_t es = hipStreamSynchronize(st);
-            if (e == hipSuccess) e = es;
-            return e == hipSuccess ? KNN_OK : KNN_EHIP;
-        });
+    const Column<DeviceSpace>* grp = live;
+    auto fill_rows = [&](int i, void* dst, const void* src) {
+        const size_t row = grp[i].stride;
+        if (old && src) e = hipMemcpyAsync(dst, src, old * row, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemsetAsync((char*)dst + old * row, 0, ((size_t)ncap - old) * row, st);
+        return e == hipSuccess ? KNN_OK : KNN_EHIP;
+    };
+    auto wait_rows = [&]() {
+        const hipError_t es = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = es;
+        return e == hipSuccess ? KNN_OK : KNN_EHIP;
+    };
+    const int rc = regrow_columns(live, n, (size_t)ncap, fill_rows, wait_rows);
     if (rc != KNN_OK && e == hipSuccess) {   // no fill or wait failed: an allocation did
         (void)hipGetLastError();
         KNN_FAIL(KNN_ENOMEM, "hipMalloc of the %lld-row corpus buffers failed", (long long)ncap);
     }
     if (rc != KNN_OK) KNN_FAIL(KNN_EHIP, "corpus regrowth failed: %s", hipGetErrorString(e));
     ix->cap = ncap;
+    if (n_tail > 0) {
+        grp = live + n;
+        if (regrow_columns(grp, n_tail, (size_t)ncap, fill_rows, wait_rows) != KNN_OK) {
+            (void)hipGetLastError();
+            ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();
+            ix->xt_state = 0;                  // the next large-batch search builds it again
+            ix->xt_tried = false;
+        }
+    }
     return KNN_OK;
 }
 
@@ -139,6 +156,11 @@ int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st) 
     if (ix->x8)
         KNN_HIP(launch_i8_rows(xb, n, ix->dp, ix->nblk8, (int8_t*)at(kColX8), (float*)at(kColX8s),
                                (float*)at(kColX8r), st));
+    if (ix->xt) {
+        KNN_HIP(launch_i8tail_rows(xb, n, ix->dp, ix->dpb, ix->xt_head, ix->xt_dpt, (int8_t*)at(kColXt),
+                                   (float*)at(kColXts), (float4*)at(kColXtm), st));
+        ix->xt_tried = false;        // new rows can move the copy's maxima: the next search is a trial again
+    }
     ix->ntotal += n;
     ix->xn_max_stale = true;
     return KNN_OK;
@@ -169,6 +191,44 @@ int ensure_i8(knn_index* ix, hipStream_t st) {
     ix->xn_max_stale = true;             // refresh_maxima computes the int8 residual maximum
     if (ix->ntotal > 0)
         KNN_HIP(launch_i8_rows(ix->xb, ix->ntotal, ix->dp, ix->nblk8, ix->x8, ix->x8s, ix->x8r, st));
+    return KNN_OK;
+}
+
+// The int8 tail copy of the 256 x 256 kernel (dpt bytes + a scale + four statistics per row: 1.8 GB
+// per 1M x 1968 rows) is built on the first search that takes the route, from the stored fp32
+// rows, and kept up to date by later adds (the int8 scan copy's pattern).  The split column comes
+// from the corpus as it stands then (i8t_pick_head), which costs one host wait for the block
+// maxima; the decision — eligible or not — then holds until knn_reset.
+int ensure_i8tail(knn_index* ix, hipStream_t st) {
+    if (ix->xt_state != 0) return KNN_OK;
+    if (ix->ntotal <= 0 || !ix->b16_ok || ix->dpb > 4096) { ix->xt_state = -1; return KNN_OK; }
+    const int nblk = ix->dpb / kB16Pad;
+    DevBuf<float> dmax;
+    int rc;
+    if ((rc = dmax.reserve((size_t)nblk)) != KNN_OK) return rc;
+    std::vector<float> hmax((size_t)nblk);
+    KNN_HIP(launch_block_absmax(ix->xb, ix->ntotal, ix->dp, nblk, dmax, st));
+    KNN_HIP(hipMemcpyAsync(hmax.data(), dmax, (size_t)nblk * sizeof(float), hipMemcpyDeviceToHost, st));
+    KNN_HIP(hipStreamSynchronize(st));
+    const int head = i8t_pick_head(hmax.data(), nblk);
+    if (head < 0) { ix->xt_state = -1; return KNN_OK; }
+    ix->xt_head = head;
+    ix->xt_dpt = (int)round_up(ix->dpb - head, 128);
+    // no room for the copy: the index searched on the bf16 pass before and goes on doing so
+    if (materialise_columns(ix, kColXt, 3) != KNN_OK) {
+        ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();
+        ix->xt_head = ix->xt_dpt = 0;
+        ix->xt_state = -1;
+        return KNN_OK;
+    }
+    // (pad rows of the codes and scales are read by the kernel's partial tiles: zero)
+    KNN_HIP(hipMemsetAsync(ix->xt, 0, (size_t)ix->cap * ix->xt_dpt, st));
+    KNN_HIP(hipMemsetAsync(ix->xts, 0, (size_t)ix->cap * sizeof(float), st));
+    KNN_HIP(hipMemsetAsync(ix->xtm, 0, (size_t)ix->cap * sizeof(float4), st));
+    ix->xn_max_stale = true;             // refresh_maxima computes the copy's maxima
+    KNN_HIP(launch_i8tail_rows(ix->xb, ix->ntotal, ix->dp, ix->dpb, head, ix->xt_dpt, ix->xt, ix->xts,
+                               ix->xtm, st));
+    ix->xt_state = 1;
     return KNN_OK;
 }
 
@@ -226,6 +286,10 @@ int create_single(int d, int metric, int device, knn_index** out) {
     if (const char* e = test_knob("IMGREC_MERGE_SINGLE")) ix->merge_single = *e != '0';
     if (const char* e = test_knob("IMGREC_STREAM_LISTS")) ix->stream_lists = *e != '0';
     if (const char* e = test_knob("IMGREC_B16W_SHARED_BOUND")) ix->shared_bound = *e != '0';
+    if (const char* e = test_knob("IMGREC_B16W_I8TAIL")) {
+        ix->i8tail = *e != '0';
+        ix->xt_no_trial = *e == '2';
+    }
     // IMGREC_RANGE_CAP=<entries> (tests): the range search's initial append capacity, so small
     // shapes reach the overflow re-run
     if (const char* e = test_knob("IMGREC_RANGE_CAP")) {
@@ -399,6 +463,20 @@ int knn_reset(knn_index_t* ix) {
     if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
     if (ix->multi) return multi_reset(ix);
     IndexOp op(ix);
+    // the int8 tail copy goes with the rows its split column was chosen from (it is read by searches
+    // that may still run: wait for them before the blocks are released)
+    if (ix->xt_state != 0) {
+        int rc = ix->xt ? op.begin_host() : KNN_OK;
+        if (rc == KNN_OK && ix->xt) rc = HipStreams::fail(hipStreamSynchronize(ix->stream), "hipStreamSynchronize");
+        if (rc != KNN_OK) return op.finish(rc);
+        ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();
+        ix->xt_state = 0;
+        ix->xt_tried = false;
+        ix->xt_head = ix->xt_dpt = 0;
+        ix->ntotal = 0;
+        ix->xn_max_stale = true;
+        return op.finish_synced(KNN_OK);
+    }
     ix->ntotal = 0;
     ix->xn_max_stale = true;
     return KNN_OK;
@@ -742,7 +820,9 @@ int knn_plan_kernel(const knn_index_t* cix, int64_t nq, int k, char* name, int c
     } else if (use_b16(ix, cn, k)) {
         const Plan p = make_b16_plan(ix->ntotal, cn, k, ix->cus, ix->dpb);
         if (p.big)
-            std::snprintf(name, cap, "knn_b16w_tile_kernel<%d, %d, %s>", p.km, l2, p.ib > 0 ? "true" : "false");
+            std::snprintf(name, cap, "knn_b16w_tile_kernel%s<%d, %d, %s>",
+                          ix->xt_state == 1 && use_i8tail(ix, cn, k) ? "_i8t" : "", p.km, l2,
+                          p.ib > 0 ? "true" : "false");
         else
             std::snprintf(name, cap, "knn_tile_topk_kernel<%d, %d, ..., %d, ...>", p.wr, p.wq, kModeBF16);
     } else if (use_split(ix, cn, k)) {
@@ -753,6 +833,30 @@ int knn_plan_kernel(const knn_index_t* cix, int64_t nq, int k, char* name, int c
         std::snprintf(name, cap, "knn_tile_topk_kernel<%d, %d, ..., %d, ...>", p.wr, p.wq, kModeF32);
     }
     return KNN_OK;
+}
+
+/* Read-only view of the int8 tail copy for tests (NULL outputs are skipped): the split column and
+ * codes per row, and rows [i0, i0 + n) of the codes (n x dpt), scales (n) and statistics (n x 4).
+ * KNN_EINVAL while the copy does not exist. */
+int knn_debug_i8tail(knn_index_t* ix, int* head, int* dpt, int64_t i0, int64_t n, int8_t* codes,
+                     float* scales, float* stats) {
+    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
+    if (ix->multi) KNN_FAIL(KNN_EINVAL, "knn_debug_i8tail: single-device indexes only");
+    IndexOp op(ix);
+    if (ix->xt_state != 1 || !ix->xt) KNN_FAIL(KNN_EINVAL, "the index has no int8 tail copy");
+    if (i0 < 0 || n < 0 || i0 + n > ix->ntotal) KNN_FAIL(KNN_EINVAL, "rows outside [0, ntotal)");
+    if (head) *head = ix->xt_head;
+    if (dpt) *dpt = ix->xt_dpt;
+    int rc = op.begin_host();
+    auto down = [&](void* dst, const void* src, size_t row) {
+        if (rc == KNN_OK && dst && n > 0)
+            rc = HipStreams::fail(hipMemcpyAsync(dst, (const char*)src + (size_t)i0 * row, (size_t)n * row,
+                                                 hipMemcpyDeviceToHost, ix->stream), "hipMemcpyAsync");
+    };
+    down(codes, ix->xt.get(), (size_t)ix->xt_dpt);
+    down(scales, ix->xts.get(), sizeof(float));
+    down(stats, ix->xtm.get(), sizeof(float4));
+    return op.finish(rc);
 }
 
 }  // extern "C"

@@ -52,6 +52,13 @@ struct QueryBounds {
     float qn, xm, nn, e_ip, c_fp, c_trunc;
     int metric;
     static constexpr float u = 1.0f / 8388608.f;   // 2^-23
+    // the bf16 / int8 inner-product bound of both constructors: a per-query value the query prep
+    // computed (e_ip_q >= 0: the int8-tail pass, i8tail_e_ip below), else the whole-row expression
+    static __device__ __forceinline__ float e_ip_of(float e_ip_q, float sq, float X, float R, float dq,
+                                                    float c_acc) {
+        if (e_ip_q >= 0.f) return e_ip_q;
+        return (sq * R + dq * (X + R) + c_acc * (sq + dq) * (X + R)) * (1.f + 1.0f / 256.f) + 1e-30f;
+    }
     __device__ __forceinline__ QueryBounds(const RerankArgs& a, int64_t q) {
         metric = a.metric;
         qn = a.qnorm[q];
@@ -69,7 +76,7 @@ struct QueryBounds {
         if (a.mode == kModeBF16 || a.mode == kModeI8) {
             const float sq = sqrtf(qn), X = sqrtf(xm), R = *a.xr_max;
             const float dq = a.q_resid ? a.q_resid[q] : 0.f;
-            e_ip = (sq * R + dq * (X + R) + a.c_split * (sq + dq) * (X + R)) * (1.f + 1.0f / 256.f) + 1e-30f;
+            e_ip = e_ip_of(a.e_ip ? a.e_ip[q] : -1.f, sq, X, R, dq, a.c_split);
         } else {
             e_ip = a.c_split * nn;
         }
@@ -93,7 +100,7 @@ struct QueryBounds {
     // The bf16 bound from its inputs (the query prep kernels: no RerankArgs yet); the same
     // expressions as the constructor above.
     __device__ __forceinline__ QueryBounds(int metric_, float qn_, float xm_, float R, float dq,
-                                           float c_acc, float c_fp_, float c_trunc_) {
+                                           float c_acc, float c_fp_, float c_trunc_, float e_ip_q = -1.f) {
         metric = metric_;
         qn = qn_;
         xm = xm_;
@@ -101,7 +108,7 @@ struct QueryBounds {
         c_trunc = c_trunc_;
         nn = sqrtf(qn) * sqrtf(xm) * (1.f + 1.0f / 1024.f) + 1e-30f;
         const float sq = sqrtf(qn), X = sqrtf(xm);
-        e_ip = (sq * R + dq * (X + R) + c_acc * (sq + dq) * (X + R)) * (1.f + 1.0f / 256.f) + 1e-30f;
+        e_ip = e_ip_of(e_ip_q, sq, X, R, dq, c_acc);
     }
     // prefix_limit is affine in |a|: prefix_limit(a) = a + A0 + B0 |a|.  The shared screen bound
     // (knn_b16w.hip) evaluates L(U) = U + (A + B |U|) in fp32 with A = A0 (1 + 2^-8) and B = B0 (1 +
@@ -123,10 +130,31 @@ struct QueryBounds {
 // One wave's reset of a query's shared screen bound record (SharedBoundPrep; lanes 0 .. kSBWords -
 // 1 write one word each): every slot and the screen floor empty, the limit coefficients fresh,
 // the other words 0 (layout: knn_kernels.h kSBWords).
+// |approximate q.x - q.x| of the int8-tail pass (knn_b16w_tile_kernel_i8t) for one query, per
+// segment (t = the int8 tail, h = the bf16 head): with x~ the stored row (s c | bf16) and q~ the
+// query's (s_q c_q | bf16),
+//   q.x - q~.x~ = q_t.(x_t - x~_t) + (q_t - q~_t).x~_t + the same for the head
+//              <= |q_t| R_t + dq_t (X_t + R_t) + |q_h| R_h + dq_h (X_h + R_h)      (Cauchy-Schwarz)
+// with R, X the corpus maxima of the rows' residuals and segment norms (stored rounded up) and dq the
+// query's residuals.  Arithmetic: the int32 sum of the code products is exact (127^2 dpt < 2^31); its
+// conversion to fp32 rounds once (above 2^24), the fold float(sum) * s_row * s_q twice more, each
+// relative to a value of at most |q~_t| |x~_t|; the head then adds H / 32 fp32 MFMA accumulations,
+// counted as the bf16 pass counts them (5 roundings per 16 columns + 16, unit roundoff 2^-23), each
+// relative to a partial sum of at most |q~| |x~| <= (|q| + dq)(X + R).  So c_acc = 1.02 (5 H / 16 +
+// 16 + 3) 2^-23 (knn_plan.cpp i8t_acc_coef).  Inflated by 1 + 2^-8 for this fp32 evaluation, as
+// QueryBounds::e_ip_of.
+__device__ __forceinline__ float i8tail_e_ip(float q, float q_t, float q_h, float dq_t, float dq_h,
+                                             float R_t, float R_h, float X_t, float X_h, float X,
+                                             float c_acc) {
+    const float dq = dq_t + dq_h, R = R_t + R_h;
+    return (q_t * R_t + dq_t * (X_t + R_t) + q_h * R_h + dq_h * (X_h + R_h) + c_acc * (q + dq) * (X + R)) *
+               (1.f + 1.0f / 256.f) + 1e-30f;
+}
+
 __device__ __forceinline__ void shared_bound_reset(const SharedBoundPrep& sb, int64_t row, int lane,
-                                                   float qn, float dq) {
+                                                   float qn, float dq, float e_ip_q = -1.f) {
     if (lane >= kSBWords) return;
-    const QueryBounds B(sb.metric, qn, *sb.xn_max, *sb.xr_max, dq, sb.c_acc, sb.c_fp, sb.c_trunc);
+    const QueryBounds B(sb.metric, qn, *sb.xn_max, *sb.xr_max, dq, sb.c_acc, sb.c_fp, sb.c_trunc, e_ip_q);
     float A, Bc;
     B.limit_coefs(A, Bc);
     sb.rec[row * kSBWords + lane] = lane == kSBCoef ? __float_as_uint(A)

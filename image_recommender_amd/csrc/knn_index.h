@@ -117,6 +117,12 @@ int split_kc(int k);
 float split_coef(int dp);
 float rerank_coef(int dp);
 float b16_acc_coef(int dpb);
+// int8 tail of the 256 x 256 kernel (knn_b16w_tile_kernel_i8t): the accumulation coefficient of a
+// pass with `head` bf16 columns (knn_certify.h i8tail_e_ip), and the split column from the corpus's
+// per-block max |x| (nblk = dpb / 64 blocks): a multiple of 64, or -1 = the route is off
+float i8t_acc_coef(int head);
+int i8t_pick_head(const float* blkmax, int nblk);
+constexpr int kI8TMinTail = 512;               // tail columns below which the route is off
 // int8 small-batch pass (knn_i8.hip): batches of at most kI8MaxQ queries, K' = kB16Cand
 constexpr int kI8MaxQ = 8;
 float i8_acc_coef(int nblk);
@@ -166,6 +172,8 @@ struct knn_index {
     // IMGREC_B16W_SHARED_BOUND=0: the 256 x 256 bf16 kernel's lists screen each on their own (no
     // shared per-query bound, TileArgs::sbound)
     bool shared_bound = true;
+    // IMGREC_B16W_I8TAIL=0: AUTO / i8 large batches stay on the pure bf16 256 x 256 kernel
+    bool i8tail = true;
     bool rerank_nw4 = false;    // IMGREC_RERANK_NW4=1: large batches rerank on 4-wave workgroups
     bool rerank_p1k = true;     // large batches rerank k rows first (IMGREC_RERANK_P1=0: 16)
     bool i8_fused_prep = true;  // int8 query prep inside the scan (IMGREC_I8_FUSED_PREP=0: own launch)
@@ -181,6 +189,21 @@ struct knn_index {
     DevBuf<float> x8s;    // cap x nblk8 block scales
     DevBuf<float> x8r;    // cap: |x - s c| per row
     DevBuf<float> x8r_max;   // device scalar, max of x8r
+    // int8 tail copy of the 256 x 256 kernel (built by the first search that takes the route,
+    // ensure_i8tail; DESIGN.md "int8 tail"): columns xt_head .. dpb - 1 of every row
+    DevBuf<int8_t> xt;       // cap x xt_dpt codes, natural column order, pad 0
+    DevBuf<float> xts;       // cap: scale max|x_tail| / 127
+    DevBuf<float4> xtm;      // cap: (|x_tail - s c|, |x_head - bf16(x_head)|, |x_tail|, |x_head|), rounded up
+    DevBuf<float> xt_max;    // device: the four maxima of xtm (R_t, R_h, X_t, X_h)
+    int xt_state = 0;        // 0 = not decided yet (until reset), 1 = built, -1 = the index is not eligible
+    int xt_head = 0, xt_dpt = 0;
+    // the copy's first search is a trial: its certificate counts decide whether the index keeps the
+    // route (search_locked); false again after reset
+    bool xt_tried = false;
+    bool xt_no_trial = false;   // IMGREC_B16W_I8TAIL=2: no trial (measurement builds whose lists are wrong)
+    DevBuf<int8_t> qt;       // a search's query tail codes, scales and inner-product bounds
+    DevBuf<float> qts;
+    DevBuf<float> q_eip;
     int nblk8 = 0;           // 64-element blocks per row (d <= 4096)
     DevBuf<int8_t> q8;        // a search's two-level query codes
     DevBuf<float> q8s;       //   their scales
@@ -310,12 +333,17 @@ int fetch_results(knn_index* ix, int64_t nq, int k, float* D, int64_t* I);
 // that lists them.  Fills cols with the live ones (the split and int8 copies once materialised, the
 // bf16 copy where enabled: what follows every add, regrowth and removal) and returns their number;
 // all = true: with every column, at its kCol index.
-enum { kColXb, kColXn, kColXs, kColXh, kColXr, kColX8, kColX8s, kColX8r, kCorpusColumns };
+enum { kColXb, kColXn, kColXs, kColXh, kColXr, kColX8, kColX8s, kColX8r, kColXt, kColXts, kColXtm, kCorpusColumns };
 int corpus_columns(knn_index* ix, Column<DeviceSpace>* cols, bool all = false);
 int reserve_rows(knn_index* ix, int64_t need, hipStream_t st);
 int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st);
 int ensure_split(knn_index* ix, hipStream_t st);
 int ensure_i8(knn_index* ix, hipStream_t st);
+// the int8 tail copy: decides the index's eligibility and split column once (a host wait for the
+// corpus statistics), builds the copy; xt_state says which.  use_i8tail: the route's conditions
+// that need no build (mode, knob, plan)
+int ensure_i8tail(knn_index* ix, hipStream_t st);
+bool use_i8tail(const knn_index* ix, int64_t nq, int k);
 int create_single(int d, int metric, int device, knn_index** out);
 void free_single(knn_index* ix);
 // knn_search.cpp

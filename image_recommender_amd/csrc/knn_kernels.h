@@ -35,6 +35,15 @@ struct TileArgs {
     // 256 x 256 bf16 kernel, optional: the shared screen bound's per-query records (nq_pad x
     // kSBWords, reset by the query prep: SharedBoundPrep); NULL = every list screens alone
     uint32_t* sbound = nullptr;
+    // 256 x 256 bf16 kernel, optional: the int8 tail (knn_b16w_tile_kernel_i8t; DESIGN.md "int8
+    // tail").  xt non-NULL: columns t_head .. of every row and query come from the int8 tail copy
+    // (t_dpt codes per row, one scale per row / per query), only the first t_head columns from
+    // xb / qp
+    const int8_t* xt = nullptr;
+    const float* xts = nullptr;
+    const int8_t* qt = nullptr;     // nq_pad x t_dpt query codes
+    const float* qts = nullptr;     // nq_pad query scales
+    int t_head = 0, t_dpt = 0;
 };
 
 // Shared screen bound of the 256 x 256 bf16 kernel (knn_b16w.hip, DESIGN.md "Shared screen
@@ -55,6 +64,20 @@ struct SharedBoundPrep {
     const float* xr_max = nullptr;
     float c_acc = 0.f, c_fp = 0.f, c_trunc = 0.f;   // RerankArgs::c_split, c_fp, c_trunc
     int metric = 0, km = 0;     // km: the candidate kernel's list length = slots per query
+};
+
+// The int8 tail's query side, written by the same prep pass (launch_query_prep_b16) when codes is
+// set: columns head .. dpb - 1 of every query as int8 codes with one scale per query (dpt codes
+// per query, pad codes 0), and the query's inner-product error bound e_ip of the int8-tail pass
+// (RerankArgs::e_ip) from the corpus maxima xt_max = (R_t, R_h, X_t, X_h).
+struct I8TailPrep {
+    int8_t* codes = nullptr;    // nq_pad x dpt; NULL = nothing to do
+    float* scale = nullptr;     // nq_pad
+    float* e_ip = nullptr;      // nq_pad
+    const float* xt_max = nullptr;
+    const float* xn_max = nullptr;
+    int head = 0, dpt = 0;
+    float c_acc = 0.f;          // i8t_acc_coef(head)
 };
 
 // One rerank + certificate launch over merged candidate-pass candidates (knn_refine.hip).
@@ -81,6 +104,9 @@ struct RerankArgs {
     const float* q_resid;       // kModeBF16: |q - bf16(q)| per query (kModeI8: NULL, fp32 query)
     const float* xr_max;        // kModeBF16: device scalar, max over rows of |x - bf16(x)|;
                                 // kModeI8: max over rows of |x - s c| (the int8 copy's residual)
+    // optional: |approximate q.x - q.x| per query, computed by the query prep (the int8-tail pass:
+    // I8TailPrep::e_ip); set = it replaces the bound from q_resid / xr_max / c_split
+    const float* e_ip = nullptr;
     float* floor;               // per query: smallest key any row outside the candidates can
                                 // have besides the K'-th candidate's (merge "floor"), or NULL
     // the candidate kernel's shared screen bound records (TileArgs::sbound), or NULL: word kSBFloor
@@ -324,7 +350,17 @@ hipError_t launch_bf16_rows(const float* src, int64_t n, int dp, int dpb, uint16
 // (dpb <= 4096; hipErrorInvalidValue otherwise, the caller then uses the two kernels above)
 hipError_t launch_query_prep_b16(const float* src, int64_t n, int d, int dp, int dpb, int64_t n_pad,
                                  int normalize, float* dst, float* norms, uint16_t* qb, float* resid,
-                                 hipStream_t st, const SharedBoundPrep* sb = nullptr);
+                                 hipStream_t st, const SharedBoundPrep* sb = nullptr,
+                                 const I8TailPrep* tp = nullptr);
+// The int8 tail copy of the 256 x 256 kernel (knn_i8t.hip; DESIGN.md "int8 tail").
+// corpus-wide max |x| of every 64-column block (nblk floats at out, zeroed here)
+hipError_t launch_block_absmax(const float* xb, int64_t n, int dp, int nblk, float* out, hipStream_t st);
+// rows' columns head .. dpb - 1 -> dpt int8 codes (pad 0) + scale max|x_tail| / 127 per row, and per
+// row stat = (|x_tail - s c|, |x_head - bf16(x_head)|, |x_tail|, |x_head|), each rounded up
+hipError_t launch_i8tail_rows(const float* xb, int64_t n, int dp, int dpb, int head, int dpt,
+                              int8_t* codes, float* scale, float4* stat, hipStream_t st);
+// out[0..3] = the component-wise maxima of n rows' stat (R_t, R_h, X_t, X_h)
+hipError_t launch_i8tail_max(const float4* stat, int64_t n, float* out, hipStream_t st);
 hipError_t launch_max_norm(const float* xn, int64_t n, float* out, hipStream_t st);
 
 // IVF-PQ (ivfpq.hip; layouts in include/imgrec_ivfpq.h)

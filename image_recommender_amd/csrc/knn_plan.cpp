@@ -1,8 +1,10 @@
 // knn_plan.cpp — launch geometry of the fused distance + top-k kernels and the relative
 // error-bound coefficients of the candidate paths' certificate (DESIGN.md "Launch plan",
 // "bf16 path", "Split path").
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <vector>
 
 #include "knn_index.h"
 
@@ -79,6 +81,30 @@ float rerank_coef(int dp) {
 float b16_acc_coef(int dpb) {
     return (float)(1.02 * (5.0 * (dpb / 16) + 16.0) * std::ldexp(1.0, -23));
 }
+// int8 tail of the 256 x 256 kernel: derived at knn_certify.h i8tail_e_ip
+float i8t_acc_coef(int head) {
+    return (float)(1.02 * (5.0 * (head / 16) + 16.0 + 3.0) * std::ldexp(1.0, -23));
+}
+
+// The int8 tail's split column H from the corpus-wide max |x| of each 64-column block: the
+// smallest block boundary such that every block at or after it is within 2x of the (lower) median
+// of those blocks: one scale per row then fits the whole tail, and large leading parts stay in
+// bf16.  The route is off (-1) when fewer than kI8TMinTail tail columns remain or the head would be
+// more than half the row.
+int i8t_pick_head(const float* blkmax, int nblk) {
+    for (int j = 0; j < nblk; ++j) {
+        std::vector<float> v(blkmax + j, blkmax + nblk);
+        std::nth_element(v.begin(), v.begin() + (v.size() - 1) / 2, v.end());
+        const float med = v[(v.size() - 1) / 2];
+        bool ok = true;
+        for (int b = j; b < nblk && ok; ++b) ok = blkmax[b] <= 2.f * med && 2.f * blkmax[b] >= med;
+        if (!ok) continue;
+        const int head = 64 * j, dpb = 64 * nblk;
+        return dpb - head >= kI8TMinTail && head <= dpb / 2 ? head : -1;
+    }
+    return -1;
+}
+
 // int8 small-batch pass (knn_i8.hip): per block an exact int32 dot of the row's and the query's
 // codes per level (exact in fp32 as well, |D| < 2^24), the fold s_x (s_hi D_hi + s_lo D_lo) into
 // the lane's accumulator (three roundings), ceil(nblk/16) blocks per lane, then the 16-lane DPP

@@ -109,6 +109,120 @@ bf16_rows_kernel(const float* __restrict__ src, int64_t n, int dp, int dpb,
     if (sb.rec) shared_bound_reset(sb, row, lane, sb.qnorm[row], sqrtf(acc));
 }
 
+// ---- the int8 tail copy of the 256 x 256 kernel (DESIGN.md "int8 tail") ----------------------
+// Corpus-wide max |x| per 64-column block: a workgroup takes 256 rows, a wave's lanes 64
+// consecutive columns (one block), so one atomic per wave and block (values >= 0: their bits
+// order like unsigned integers).
+__global__ void __launch_bounds__(256)
+block_absmax_kernel(const float* __restrict__ xb, int64_t n, int dp, int nblk, float* __restrict__ out) {
+    const int64_t r0 = (int64_t)blockIdx.x * 256, r1 = r0 + 256 < n ? r0 + 256 : n;
+    for (int j = threadIdx.x; j < 64 * nblk; j += 256) {
+        float m = 0.f;
+        if (j < dp)
+            for (int64_t r = r0; r < r1; ++r) m = fmaxf(m, fabsf(xb[r * dp + j]));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+        if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<unsigned*>(out) + j / 64, __float_as_uint(m));
+    }
+}
+
+// 8 elements of an fp32 row at chunk c (zero past dp)
+__device__ __forceinline__ void load_chunk8(const float* x, int c, int dp, float (&e)[8]) {
+    if (8 * c + 8 <= dp) {
+        const float4 v0 = *reinterpret_cast<const float4*>(x + 8 * c);
+        const float4 v1 = *reinterpret_cast<const float4*>(x + 8 * c + 4);
+        e[0] = v0.x; e[1] = v0.y; e[2] = v0.z; e[3] = v0.w;
+        e[4] = v1.x; e[5] = v1.y; e[6] = v1.z; e[7] = v1.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) e[j] = (8 * c + j < dp) ? x[8 * c + j] : 0.f;
+    }
+}
+
+// One wave per row: columns head .. dpb - 1 -> int8 codes c = rint(x / s), s = max |x_tail| / 127
+// (an all-zero tail: s = 0, codes 0), dpt codes per row with the pad 0, and the row's stat =
+// (|x_tail - s c|, |x_head - bf16(x_head)|, |x_tail|, |x_head|), each rounded up (1 + 2^-9 covers
+// the fp32 accumulation of at most dpb / 64 + 6 terms per lane).
+__global__ void __launch_bounds__(256)
+i8tail_rows_kernel(const float* __restrict__ src, int64_t n, int dp, int dpb, int head, int dpt,
+                   int8_t* __restrict__ codes, float* __restrict__ scales, float4* __restrict__ stat) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const float* x = src + row * dp;
+    const int hc = head / 8;
+    float amax = 0.f, nh = 0.f, nt = 0.f, rh = 0.f, rt = 0.f;
+    for (int c = lane; c < dpb / 8; c += 64) {
+        float e[8];
+        load_chunk8(x, c, dp, e);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            if (c < hc) {
+                const float r = e[t] - __uint_as_float(bf16_rne(e[t]) << 16);
+                nh = fmaf(e[t], e[t], nh);
+                rh = fmaf(r, r, rh);
+            } else {
+                nt = fmaf(e[t], e[t], nt);
+                amax = fmaxf(amax, fabsf(e[t]));
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    const float sc = amax / 127.f, inv = amax > 0.f ? 127.f / amax : 0.f;
+    int8_t* oc = codes + row * dpt;
+    for (int c = hc + lane; c < hc + dpt / 8; c += 64) {
+        uint32_t w[2] = {0u, 0u};
+        if (c < dpb / 8) {
+            float e[8];
+            load_chunk8(x, c, dp, e);
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const float cf = fminf(fmaxf(rintf(e[t] * inv), -127.f), 127.f);
+                const float r = fmaf(-sc, cf, e[t]);
+                rt = fmaf(r, r, rt);
+                w[t >> 2] |= ((uint32_t)(int)cf & 0xffu) << (8 * (t & 3));
+            }
+        }
+        *reinterpret_cast<uint2*>(oc + 8 * (c - hc)) = make_uint2(w[0], w[1]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        nh += __shfl_xor(nh, off, 64);
+        nt += __shfl_xor(nt, off, 64);
+        rh += __shfl_xor(rh, off, 64);
+        rt += __shfl_xor(rt, off, 64);
+    }
+    if (lane == 0) {
+        const float up = 1.f + 1.0f / 512.f;
+        scales[row] = sc;
+        stat[row] = make_float4(sqrtf(rt) * up, sqrtf(rh) * up, sqrtf(nt) * up, sqrtf(nh) * up);
+    }
+}
+
+__global__ void i8tail_max_kernel(const float4* __restrict__ stat, int64_t n, float* __restrict__ out) {
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const float4 v = stat[i];
+        m = make_float4(fmaxf(m.x, v.x), fmaxf(m.y, v.y), fmaxf(m.z, v.z), fmaxf(m.w, v.w));
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        m.x = fmaxf(m.x, __shfl_xor(m.x, off, 64));
+        m.y = fmaxf(m.y, __shfl_xor(m.y, off, 64));
+        m.z = fmaxf(m.z, __shfl_xor(m.z, off, 64));
+        m.w = fmaxf(m.w, __shfl_xor(m.w, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        unsigned* o = reinterpret_cast<unsigned*>(out);
+        atomicMax(o, __float_as_uint(m.x));
+        atomicMax(o + 1, __float_as_uint(m.y));
+        atomicMax(o + 2, __float_as_uint(m.z));
+        atomicMax(o + 3, __float_as_uint(m.w));
+    }
+}
+
 // One wave per query row, the bf16 path's whole query side in one pass: raw row (d floats) ->
 // padded fp32 row (dp, zero tail; L2-normalised when `normalize`, faiss fvec_renorm_L2 scale), its
 // |q|^2, the bf16 row (dpb, RNE) and |q - bf16(q)|.  Rows n..n_pad-1 are zero.  Each lane holds
@@ -118,7 +232,7 @@ __global__ void __launch_bounds__(256)
 query_prep_b16_kernel(const float* __restrict__ src, int64_t n, int d, int dp, int dpb,
                       int64_t n_pad, int normalize, float* __restrict__ dst,
                       float* __restrict__ norms, uint16_t* __restrict__ qb,
-                      float* __restrict__ resid, const SharedBoundPrep sb) {
+                      float* __restrict__ resid, const SharedBoundPrep sb, const I8TailPrep tp) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= n_pad) return;
@@ -187,8 +301,70 @@ query_prep_b16_kernel(const float* __restrict__ src, int64_t n, int d, int dp, i
         norms[row] = nacc;
         resid[row] = sqrtf(racc);
     }
+    // the int8 tail (I8TailPrep): columns tp.head .. as int8 codes with one scale, and the query's
+    // e_ip of that pass.  Chunks of 8 lie wholly in the head or the tail (tp.head % 64 == 0).
+    float e_ip_q = -1.f;
+    if (tp.codes) {
+        const int hc = tp.head / 8;
+        float amax = 0.f, nh = 0.f, nt = 0.f, rh = 0.f;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int c = lane + 64 * it;
+            if (8 * c >= dpb) continue;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const float v = normalize ? e[it][t] * scale : e[it][t];
+                if (c < hc) {
+                    const float r = v - __uint_as_float(bf16_rne(v) << 16);
+                    nh = fmaf(v, v, nh);
+                    rh = fmaf(r, r, rh);
+                } else {
+                    nt = fmaf(v, v, nt);
+                    amax = fmaxf(amax, fabsf(v));
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+        const float sc = amax / 127.f, inv = amax > 0.f ? 127.f / amax : 0.f;
+        float rt = 0.f;
+        int8_t* oc = tp.codes + row * tp.dpt;
+#pragma unroll
+        for (int it = 0; it < IT; ++it) {
+            const int c = lane + 64 * it;
+            if (8 * c >= dpb || c < hc) continue;
+            uint32_t w[2] = {0u, 0u};
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const float v = normalize ? e[it][t] * scale : e[it][t];
+                const float cf = fminf(fmaxf(rintf(v * inv), -127.f), 127.f);
+                const float r = fmaf(-sc, cf, v);
+                rt = fmaf(r, r, rt);
+                w[t >> 2] |= ((uint32_t)(int)cf & 0xffu) << (8 * (t & 3));
+            }
+            *reinterpret_cast<uint2*>(oc + 8 * (c - hc)) = make_uint2(w[0], w[1]);
+        }
+        for (int c = dpb / 8 + lane; c < hc + tp.dpt / 8; c += 64)      // pad codes
+            *reinterpret_cast<uint2*>(oc + 8 * (c - hc)) = make_uint2(0u, 0u);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            nh += __shfl_xor(nh, off, 64);
+            nt += __shfl_xor(nt, off, 64);
+            rh += __shfl_xor(rh, off, 64);
+            rt += __shfl_xor(rt, off, 64);
+        }
+        // (norms and residuals rounded up: 1 + 2^-9 covers their fp32 accumulation)
+        const float up = 1.f + 1.0f / 512.f;
+        const float* m = tp.xt_max;
+        e_ip_q = i8tail_e_ip(sqrtf(nacc) * up, sqrtf(nt) * up, sqrtf(nh) * up, sqrtf(rt) * up, sqrtf(rh) * up,
+                             m[0], m[1], m[2], m[3], sqrtf(*tp.xn_max) * up, tp.c_acc);
+        if (lane == 0) {
+            tp.scale[row] = sc;
+            tp.e_ip[row] = e_ip_q;
+        }
+    }
     // the candidate kernel's shared screen bound: this query's record starts empty
-    if (sb.rec) shared_bound_reset(sb, row, lane, nacc, sqrtf(racc));
+    if (sb.rec) shared_bound_reset(sb, row, lane, nacc, sqrtf(racc), e_ip_q);
 }
 
 // One workgroup of kRerankWaves waves per query.  a.cd/a.ci: the merged approximate candidates,
@@ -722,19 +898,50 @@ hipError_t launch_bf16_rows(const float* src, int64_t n, int dp, int dpb, uint16
 
 hipError_t launch_query_prep_b16(const float* src, int64_t n, int d, int dp, int dpb, int64_t n_pad,
                                  int normalize, float* dst, float* norms, uint16_t* qb, float* resid,
-                                 hipStream_t st, const SharedBoundPrep* sb) {
+                                 hipStream_t st, const SharedBoundPrep* sb, const I8TailPrep* tp) {
     if (n_pad <= 0) return hipSuccess;
     if (dpb % 8 != 0 || dp % 16 != 0 || dpb < dp || dp < d) return hipErrorInvalidValue;
+    if (tp && tp->codes &&
+        (tp->head % 64 != 0 || tp->head < 0 || tp->head >= dpb || tp->dpt % 128 != 0 ||
+         tp->dpt < dpb - tp->head || !tp->scale || !tp->e_ip || !tp->xt_max || !tp->xn_max))
+        return hipErrorInvalidValue;
     const dim3 grid((unsigned)((n_pad + 3) / 4)), block(256);
 #define IMGREC_QPREP(ITV) hipLaunchKernelGGL((query_prep_b16_kernel<ITV>), grid, block, 0, st, src, n, \
                                              d, dp, dpb, n_pad, normalize, dst, norms, qb, resid,      \
-                                             sb ? *sb : SharedBoundPrep{})
+                                             sb ? *sb : SharedBoundPrep{}, tp ? *tp : I8TailPrep{})
     if (dpb <= 512) IMGREC_QPREP(1);
     else if (dpb <= 1024) IMGREC_QPREP(2);
     else if (dpb <= 2048) IMGREC_QPREP(4);
     else if (dpb <= 4096) IMGREC_QPREP(8);
     else return hipErrorInvalidValue;
 #undef IMGREC_QPREP
+    return hipGetLastError();
+}
+
+hipError_t launch_block_absmax(const float* xb, int64_t n, int dp, int nblk, float* out, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)nblk * sizeof(float), st);
+    if (e != hipSuccess || n <= 0) return e;
+    hipLaunchKernelGGL(block_absmax_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, xb, n, dp,
+                       nblk, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_i8tail_rows(const float* xb, int64_t n, int dp, int dpb, int head, int dpt,
+                              int8_t* codes, float* scale, float4* stat, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (dpb % 64 != 0 || dp % 8 != 0 || dpb < dp || head % 64 != 0 || head < 0 || head >= dpb ||
+        dpt % 128 != 0 || dpt < dpb - head)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(i8tail_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, xb, n, dp, dpb,
+                       head, dpt, codes, scale, stat);
+    return hipGetLastError();
+}
+
+hipError_t launch_i8tail_max(const float4* stat, int64_t n, float* out, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(out, 0, 4 * sizeof(float), st);
+    if (e != hipSuccess || n <= 0) return e;
+    const int64_t blocks = std::min<int64_t>(1024, (n + 255) / 256);
+    hipLaunchKernelGGL(i8tail_max_kernel, dim3((unsigned)blocks), dim3(256), 0, st, stat, n, out);
     return hipGetLastError();
 }
 

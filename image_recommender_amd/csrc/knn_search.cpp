@@ -98,6 +98,10 @@ int refresh_maxima(knn_index* ix, hipStream_t st) {
         if ((rc = ix->x8r_max.reserve(1)) != KNN_OK) return rc;
         KNN_HIP(launch_max_norm(ix->x8r, ix->ntotal, ix->x8r_max, st));
     }
+    if (ix->xt) {        // the int8 tail copy: R_t, R_h, X_t, X_h
+        if ((rc = ix->xt_max.reserve(4)) != KNN_OK) return rc;
+        KNN_HIP(launch_i8tail_max(ix->xtm, ix->ntotal, ix->xt_max, st));
+    }
     ix->xn_max_stale = false;
     return KNN_OK;
 }
@@ -308,9 +312,59 @@ int shared_bound_prep(knn_index* ix, const Plan& p, const float* qnorm, hipStrea
     return KNN_OK;
 }
 
+bool stream_capturing(hipStream_t st) {
+    hipStreamCaptureStatus s = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &s) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return s != hipStreamCaptureStatusNone;
+}
+
+// The int8 tail of a chunk that takes the route (search_locked, ahead of the fused query prep):
+// the copy is built if this is its first search, the maxima the prep reads are refreshed, the
+// query-side buffers grown.  tp->codes stays NULL when the chunk stays on the pure bf16 pass.
+int i8tail_prep(knn_index* ix, const Plan& p, int64_t nq, int k, hipStream_t st, I8TailPrep* tp) {
+    *tp = I8TailPrep{};
+    if (!use_i8tail(ix, nq, k)) return KNN_OK;
+    // building the copy waits on the host, which a capturing stream does not allow: such a search
+    // runs the bf16 pass and leaves the build to the next search outside a capture
+    if (ix->xt_state == 0 && stream_capturing(st)) return KNN_OK;
+    int rc;
+    if ((rc = ensure_i8tail(ix, st)) != KNN_OK || ix->xt_state != 1) return rc;
+    if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
+    if ((rc = ix->qt.reserve((size_t)p.nq_pad * ix->xt_dpt)) != KNN_OK) return rc;
+    if ((rc = ix->qts.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
+    if ((rc = ix->q_eip.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
+    tp->codes = ix->qt; tp->scale = ix->qts; tp->e_ip = ix->q_eip;
+    tp->xt_max = ix->xt_max; tp->xn_max = ix->xn_max;
+    tp->head = ix->xt_head; tp->dpt = ix->xt_dpt;
+    tp->c_acc = i8t_acc_coef(ix->xt_head);
+    return KNN_OK;
+}
+
+// The first search on a fresh int8 tail copy is a trial (one more host wait on top of the build's):
+// whether the int8 band of a corpus fits K' = 64 depends on how its keys are spread, which no
+// statistic of the rows tells (bench config 2, 768 homogeneous columns with every in-cluster key
+// inside the band: all 1024 queries went to the exact re-run, 35 ms a step against the bf16 pass's
+// 1.4).  The route saves about 1 us per query and an exact re-run costs about 35, so re-runs of
+// more than 1/32 of the batch eat the gain: past that share the index drops the copy and stays on
+// the bf16 pass until reset.  (The second chance is not counted: its cost per query is far below a
+// re-run's and unmeasured.)
+int i8tail_trial(knn_index* ix, int64_t nq, hipStream_t st) {
+    if (stream_capturing(st)) return KNN_OK;           // (no host wait inside a capture: judged later)
+    int acc[4] = {0, 0, 0, 0};
+    KNN_HIP(hipMemcpyAsync(acc, ix->stat + 8, sizeof(acc), hipMemcpyDeviceToHost, st));
+    KNN_HIP(hipStreamSynchronize(st));
+    ix->xt_tried = true;
+    const int64_t reruns = acc[0];
+    if (reruns * 32 <= nq) return KNN_OK;
+    ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();      // (st is drained: nothing reads them)
+    ix->xt_state = -1;
+    return KNN_OK;
+}
+
 // bf16 candidates (one bf16 MFMA per product) + exact fp32 rerank of K' = 64 + certificate.
+// i8t: the 256 x 256 kernel's int8-tail sibling (the prep wrote the query's tail codes and e_ip).
 int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,
-              int64_t* I, hipStream_t st, bool timed, bool q_ready, bool first) {
+              int64_t* I, hipStream_t st, bool timed, bool q_ready, bool first, bool i8t) {
     const int kmetric = kmetric_of(ix);
     const int kc = kB16Cand;
     const Plan p = make_b16_plan(ix->ntotal, nq, k, ix->cus, ix->dpb);
@@ -334,6 +388,11 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     a.id_offset = ix->id_offset; a.cand_d = ix->cand_d; a.cand_i = ix->cand_i; a.ncand = p.ncand;
     a.ib = p.big ? p.ib : 0;
     a.sbound = sb.rec;
+    if (i8t) {
+        if (!p.big || !q_ready || ix->xt_state != 1) KNN_FAIL(KNN_EINVAL, "int8 tail without its query prep");
+        a.xt = ix->xt; a.xts = ix->xts; a.qt = ix->qt; a.qts = ix->qts;
+        a.t_head = ix->xt_head; a.t_dpt = ix->xt_dpt;
+    }
     hipEvent_t e1 = nullptr;
     if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
     KNN_HIP(p.big ? launch_b16_big(a, st) : launch_tile_topk(a, st));
@@ -343,6 +402,7 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     r.c_split = b16_acc_coef(ix->dpb);
     r.c_trunc = a.ib > 0 ? (float)std::ldexp(1.0, a.ib - 23) : 0.f;
     r.q_resid = ix->q_resid; r.xr_max = ix->xr_max;
+    if (i8t) r.e_ip = ix->q_eip;
     r.sbound = a.sbound;
     if ((rc = merge_for_rerank(ix, nq, nlists, km, p.ncand, fuse_merge_single(ix, nlists, km), &r,
                                st)) != KNN_OK)
@@ -510,6 +570,16 @@ bool use_i8(const knn_index* ix, int64_t nq, int k) {
     return !ix->b16_ok || wide_enough || ix->ntotal * i8_row <= kI8SmallCopyBytes;
 }
 
+// The 256 x 256 kernel's int8 tail: AUTO and the i8 mode, on the big plan, unless the knob turned it
+// off at creation or the index turned out not to be eligible (ensure_i8tail; dpb <= 4096: the fused
+// query prep writes the query side).  search_mode = "bf16" stays the pure bf16 pass.
+bool use_i8tail(const knn_index* ix, int64_t nq, int k) {
+    if (!ix->i8tail || ix->xt_state < 0 || ix->dpb > 4096 || ix->ntotal <= 0) return false;
+    if (ix->mode != KNN_SEARCH_AUTO && ix->mode != KNN_SEARCH_I8) return false;
+    if (use_i8(ix, nq, k) || !use_b16(ix, nq, k)) return false;
+    return make_b16_plan(ix->ntotal, nq, k, ix->cus, ix->dpb).big;
+}
+
 bool use_split(const knn_index* ix, int64_t nq, int k) {
     if (!ix->split_ok || ix->mode == KNN_SEARCH_EXACT || split_kc(k) == 0) return false;
     if (ix->mode == KNN_SEARCH_SPLIT) return true;
@@ -533,7 +603,7 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
         KNN_HIP(launch_fill_empty(D, I, nq * (int64_t)k, kmetric, st));
         return KNN_OK;
     }
-    bool first_cand = true;
+    bool first_cand = true, any_i8t = false;
     for (int64_t c0 = 0; c0 < nq; c0 += kQueryChunk) {
         const int64_t cn = std::min(kQueryChunk, nq - c0);
         const bool i8 = use_i8(ix, cn, k);
@@ -549,7 +619,7 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
         if (c0 == 0) ix->last_path = i8 ? 3 : (b16 ? 2 : (split ? 1 : 0));
         if ((rc = ix->qpad.reserve((size_t)nq_pad * ix->dp)) != KNN_OK) return rc;
         if ((rc = ix->qnorm.reserve((size_t)nq_pad)) != KNN_OK) return rc;
-        bool q_ready = false;
+        bool q_ready = false, i8t = false;
         // fused query prep: fp32 padded rows + norms + bf16 + residuals, or for the int8 path
         // the same rows and norms + the two-level int8 codes (one short pass instead of
         // rows_ingest's latency-bound row loop and a second launch)
@@ -569,11 +639,14 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
         } else if (b16 && ix->dpb <= 4096) {
             if ((rc = ix->qb16.reserve((size_t)nq_pad * ix->dpb)) != KNN_OK) return rc;
             if ((rc = ix->q_resid.reserve((size_t)nq_pad)) != KNN_OK) return rc;
+            I8TailPrep tp;
+            if ((rc = i8tail_prep(ix, p, cn, k, st, &tp)) != KNN_OK) return rc;
+            i8t = tp.codes != nullptr;
             SharedBoundPrep sb;
             if ((rc = shared_bound_prep(ix, p, ix->qnorm, st, &sb)) != KNN_OK) return rc;
             KNN_HIP(launch_query_prep_b16(q + c0 * ix->d, cn, ix->d, ix->dp, ix->dpb, nq_pad,
                                           normalize, ix->qpad, ix->qnorm, ix->qb16, ix->q_resid, st,
-                                          &sb));
+                                          &sb, &tp));
             q_ready = true;
         } else {
             KNN_HIP(launch_rows_ingest(q + c0 * ix->d, cn, ix->d, ix->dp, nq_pad, normalize,
@@ -584,15 +657,16 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
         if (i8 || b16 || split) {
             rc = i8 ? i8_chunk(ix, i8_fused ? q + c0 * ix->d : nullptr, ix->qpad, ix->qnorm, cn, k,
                                Dc, Ic, st, true, first_cand)
-               : b16 ? b16_chunk(ix, ix->qpad, ix->qnorm, cn, k, Dc, Ic, st, true, q_ready, first_cand)
+               : b16 ? b16_chunk(ix, ix->qpad, ix->qnorm, cn, k, Dc, Ic, st, true, q_ready, first_cand, i8t)
                      : split_chunk(ix, ix->qpad, ix->qnorm, cn, k, Dc, Ic, st, true, first_cand);
             first_cand = false;
         } else {
             rc = exact_chunk(ix, ix->qpad, ix->qnorm, cn, k, Dc, Ic, st, true);
         }
         if (rc != KNN_OK) return rc;
+        any_i8t = any_i8t || i8t;
     }
-    return KNN_OK;
+    return any_i8t && !ix->xt_tried && !ix->xt_no_trial ? i8tail_trial(ix, nq, st) : KNN_OK;
 }
 
 // Totals of the last search's candidate chunks (read on the index's own stream, which it

@@ -329,8 +329,19 @@ int knn_plan(const knn_index_t* index, int64_t nq, int k, int* tile_rows, int* t
              int* splits, int* workgroups);
 
 /* Name of the fused candidate/distance kernel a search of nq queries launches, as profilers print
- * it (e.g. "knn_b16w_tile_kernel<10, 1, true>"), NUL-terminated into name[cap]. */
+ * it (e.g. "knn_b16w_tile_kernel<10, 1, true>"), NUL-terminated into name[cap].  Whether a large
+ * batch runs the int8-tail sibling ("knn_b16w_tile_kernel_i8t<...>") is decided from the corpus by
+ * the first such search (it builds the copy and judges its own certificate counts): before that
+ * search this reports the bf16 kernel, after it the kernel that later searches run. */
 int knn_plan_kernel(const knn_index_t* index, int64_t nq, int k, char* name, int cap);
+
+/* Read-only view of the int8 tail copy of the 256 x 256 candidate kernel, for tests (NULL outputs
+ * are skipped): the split column `head` and the codes per row `dpt`, and rows [i0, i0 + n) of the
+ * codes (n x dpt int8), the scales (n floats) and the per-row statistics (n x 4 floats: tail
+ * residual, head residual, tail norm, head norm, each rounded up).  KNN_EINVAL while the copy does
+ * not exist (no search has taken the route yet, or the index is not eligible). */
+int knn_debug_i8tail(knn_index_t* index, int* head, int* dpt, int64_t i0, int64_t n, int8_t* codes,
+                     float* scales, float* stats);
 
 const char* knn_last_error(void);
 const char* knn_version(void);

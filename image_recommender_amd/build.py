@@ -37,7 +37,7 @@ SOURCES = ["knn_kernels.hip", "knn_b16w.hip", "knn_refine.hip", "knn_capi.cpp", 
            "knn_search.cpp", "knn_multi.cpp", "knn_io.cpp", "ivfpq_capi.cpp", "color_hist.hip",
            "ingest.cpp", "ivfpq.hip", "knn_largek.hip", "knn_hugek.hip", "vit_fused.hip", "vit_attn.hip", "knn_i8.hip", "vit_gemm.hip",
            "knn_range.hip", "knn_filter.hip", "knn_remove.hip", "knn_kmeans.hip", "vlad.hip", "vladenc.hip", "vladtrain.hip"]
-HEADERS = ["knn_kernels.h", "knn_index.h", "dev_buf.h", "knn_multi.h", "wave_ops.h", "knn_certify.h", "lds_dma.h", "knn_b16w_body.inc", "knn_tile.h", "rows_geom.h", "rows_tile.h", "dev_workspace.h", "stream_fence.h", "../../include/imgrec_ivfpq.h",
+HEADERS = ["knn_kernels.h", "knn_consts.h", "knn_plan.h", "knn_index.h", "dev_buf.h", "knn_multi.h", "wave_ops.h", "knn_certify.h", "lds_dma.h", "knn_b16w_body.inc", "knn_tile.h", "rows_geom.h", "rows_tile.h", "dev_workspace.h", "stream_fence.h", "../../include/imgrec_ivfpq.h",
            "../../include/imgrec_knn.h", "../../include/imgrec_color.h", "../../include/imgrec_ingest.h",
            "../../include/imgrec_vit.h", "../../include/imgrec_kmeans.h", "vlad_args.h",
            "../../include/imgrec_vlad.h", "vladenc_args.h", "../../include/imgrec_vladenc.h", "vladenc_kernels.h",

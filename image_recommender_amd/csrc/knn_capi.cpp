@@ -1,9 +1,9 @@
 // knn_capi.cpp — the C ABI of include/imgrec_knn.h: index lifetime, the HBM corpus buffer, adds,
-// searches, merges, timing and stats.  The search paths live in knn_search.cpp, the launch
-// geometry in knn_plan.cpp, the file layout in knn_io.cpp, the multi-device index in
-// knn_multi.cpp.  The index's memory is owned by its DevBuf / PinBuf members (knn_index.h):
-// free_single only quiesces the device and deletes the index; the corpus's per-row arrays are
-// listed once, in corpus_columns.
+// searches, merges, timing and stats.  The search paths live in knn_search.cpp, the route choice
+// and launch geometry in knn_plan.h / knn_plan.cpp (HIP-free), the file layout in knn_io.cpp, the
+// multi-device index in knn_multi.cpp.  The index's memory is owned by its DevBuf / PinBuf members
+// (knn_index.h): free_single only quiesces the device and deletes the index; the corpus's per-row
+// arrays are listed once, in corpus_columns.
 //
 // Reference call sites each entry point replaces are listed in include/imgrec_knn.h.
 //
@@ -119,9 +119,7 @@ int reserve_rows(knn_index* ix, int64_t need, hipStream_t st) {
         grp = live + n;
         if (regrow_columns(grp, n_tail, (size_t)ncap, fill_rows, wait_rows) != KNN_OK) {
             (void)hipGetLastError();
-            ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();
-            ix->xt_state = 0;                  // the next large-batch search builds it again
-            ix->xt_tried = false;
+            drop_i8tail(ix, TailCopy::Undecided);      // the next large-batch search builds it again
         }
     }
     return KNN_OK;
@@ -200,8 +198,8 @@ int ensure_i8(knn_index* ix, hipStream_t st) {
 // from the corpus as it stands then (i8t_pick_head), which costs one host wait for the block
 // maxima; the decision — eligible or not — then holds until knn_reset.
 int ensure_i8tail(knn_index* ix, hipStream_t st) {
-    if (ix->xt_state != 0) return KNN_OK;
-    if (ix->ntotal <= 0 || !ix->b16_ok || ix->dpb > 4096) { ix->xt_state = -1; return KNN_OK; }
+    if (ix->xt_state != TailCopy::Undecided) return KNN_OK;
+    if (ix->ntotal <= 0 || !ix->b16_ok || ix->dpb > 4096) { ix->xt_state = TailCopy::Ineligible; return KNN_OK; }
     const int nblk = ix->dpb / kB16Pad;
     DevBuf<float> dmax;
     int rc;
@@ -211,14 +209,12 @@ int ensure_i8tail(knn_index* ix, hipStream_t st) {
     KNN_HIP(hipMemcpyAsync(hmax.data(), dmax, (size_t)nblk * sizeof(float), hipMemcpyDeviceToHost, st));
     KNN_HIP(hipStreamSynchronize(st));
     const int head = i8t_pick_head(hmax.data(), nblk);
-    if (head < 0) { ix->xt_state = -1; return KNN_OK; }
+    if (head < 0) { ix->xt_state = TailCopy::Ineligible; return KNN_OK; }
     ix->xt_head = head;
     ix->xt_dpt = (int)round_up(ix->dpb - head, 128);
     // no room for the copy: the index searched on the bf16 pass before and goes on doing so
     if (materialise_columns(ix, kColXt, 3) != KNN_OK) {
-        ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();
-        ix->xt_head = ix->xt_dpt = 0;
-        ix->xt_state = -1;
+        drop_i8tail(ix, TailCopy::Ineligible);
         return KNN_OK;
     }
     // (pad rows of the codes and scales are read by the kernel's partial tiles: zero)
@@ -228,8 +224,19 @@ int ensure_i8tail(knn_index* ix, hipStream_t st) {
     ix->xn_max_stale = true;             // refresh_maxima computes the copy's maxima
     KNN_HIP(launch_i8tail_rows(ix->xb, ix->ntotal, ix->dp, ix->dpb, head, ix->xt_dpt, ix->xt, ix->xts,
                                ix->xtm, st));
-    ix->xt_state = 1;
+    ix->xt_state = TailCopy::Built;
     return KNN_OK;
+}
+
+// The copy's only teardown.  The caller has drained every stream that may still read the blocks.
+// Every caller gets the whole reset, where each used to clear its own subset of xt_head, xt_dpt and
+// xt_tried: the difference cannot be observed, since all three are read only while the copy is
+// Built (searches, adds, corpus_columns' live columns, knn_debug_i8tail) or after the next
+// ensure_i8tail wrote them on its way from Undecided.
+void drop_i8tail(knn_index* ix, TailCopy next) {
+    ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();
+    ix->xt_head = ix->xt_dpt = 0;
+    ix->xt_tried = false; ix->xt_state = next;
 }
 
 int create_single(int d, int metric, int device, knn_index** out) {
@@ -465,14 +472,11 @@ int knn_reset(knn_index_t* ix) {
     IndexOp op(ix);
     // the int8 tail copy goes with the rows its split column was chosen from (it is read by searches
     // that may still run: wait for them before the blocks are released)
-    if (ix->xt_state != 0) {
+    if (ix->xt_state != TailCopy::Undecided) {
         int rc = ix->xt ? op.begin_host() : KNN_OK;
         if (rc == KNN_OK && ix->xt) rc = HipStreams::fail(hipStreamSynchronize(ix->stream), "hipStreamSynchronize");
         if (rc != KNN_OK) return op.finish(rc);
-        ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();
-        ix->xt_state = 0;
-        ix->xt_tried = false;
-        ix->xt_head = ix->xt_dpt = 0;
+        drop_i8tail(ix, TailCopy::Undecided);
         ix->ntotal = 0;
         ix->xn_max_stale = true;
         return op.finish_synced(KNN_OK);
@@ -793,45 +797,33 @@ int knn_large_k_fallbacks(const knn_index_t* cix, int64_t* n) {
     return KNN_OK;
 }
 
+// knn_plan and knn_plan_kernel format what search_locked decides for a search's first chunk.
+static_assert((int)Route::Exact == kModeF32 && (int)Route::Split == kModeSplit && (int)Route::B16 == kModeBF16,
+              "knn_plan_kernel prints a generic tile's route as its kMode");
+
 int knn_plan(const knn_index_t* cix, int64_t nq, int k, int* tr, int* tq, int* splits, int* wgs) {
     if (!cix || !tr || !tq || !splits || !wgs) KNN_FAIL(KNN_EINVAL, "NULL argument");
     const knn_index* ix = cix->multi ? multi_shard(cix, 0) : cix;
-    const int64_t cn = std::min(nq, kQueryChunk);
-    const Plan p = use_i8(ix, cn, k) ? make_i8_plan(ix->ntotal, cn, k, ix->cus, ix->i8_wgpcu, ix->nblk8)
-                 : use_b16(ix, cn, k) ? make_b16_plan(ix->ntotal, cn, k, ix->cus, ix->dpb)
-                 : use_split(ix, cn, k) ? make_split_plan(ix->ntotal, cn, split_kc(k), ix->cus)
-                                        : make_plan(ix->ntotal, cn, k, ix->cus);
-    *tr = p.bm;
-    *tq = p.bq;
-    *splits = p.nsplit;
-    *wgs = p.wgs;
+    const Plan p = choose_route(*ix, std::min(nq, kQueryChunk), k).plan;
+    *tr = p.bm; *tq = p.bq;
+    *splits = p.nsplit; *wgs = p.wgs;
     return KNN_OK;
 }
 
 int knn_plan_kernel(const knn_index_t* cix, int64_t nq, int k, char* name, int cap) {
     if (!cix || !name || cap < 1) KNN_FAIL(KNN_EINVAL, "NULL argument");
     const knn_index* ix = cix->multi ? multi_shard(cix, 0) : cix;
-    const int64_t cn = std::min(nq, kQueryChunk);
     const int l2 = ix->metric == KNN_METRIC_L2 ? 1 : 0;
-    if (use_i8(ix, cn, k)) {
-        const Plan p = make_i8_plan(ix->ntotal, cn, k, ix->cus, ix->i8_wgpcu, ix->nblk8);
-        std::snprintf(name, cap, "knn_i8_scan_kernel<%d, %d, %d>", cn <= 2 ? (int)cn : (cn <= 4 ? 4 : 8), p.km,
-                      (ix->nblk8 + 15) / 16);
-    } else if (use_b16(ix, cn, k)) {
-        const Plan p = make_b16_plan(ix->ntotal, cn, k, ix->cus, ix->dpb);
-        if (p.big)
-            std::snprintf(name, cap, "knn_b16w_tile_kernel%s<%d, %d, %s>",
-                          ix->xt_state == 1 && use_i8tail(ix, cn, k) ? "_i8t" : "", p.km, l2,
-                          p.ib > 0 ? "true" : "false");
-        else
-            std::snprintf(name, cap, "knn_tile_topk_kernel<%d, %d, ..., %d, ...>", p.wr, p.wq, kModeBF16);
-    } else if (use_split(ix, cn, k)) {
-        const Plan p = make_split_plan(ix->ntotal, cn, split_kc(k), ix->cus);
-        std::snprintf(name, cap, "knn_tile_topk_kernel<%d, %d, ..., %d, ...>", p.wr, p.wq, kModeSplit);
-    } else {
-        const Plan p = make_plan(ix->ntotal, cn, k, ix->cus);
-        std::snprintf(name, cap, "knn_tile_topk_kernel<%d, %d, ..., %d, ...>", p.wr, p.wq, kModeF32);
-    }
+    const RoutePlan rp = choose_route(*ix, std::min(nq, kQueryChunk), k);
+    const Plan& p = rp.plan;
+    if (rp.route == Route::I8)
+        std::snprintf(name, cap, "knn_i8_scan_kernel<%d, %d, %d>", rp.i8_inst, p.km, (ix->nblk8 + 15) / 16);
+    else if (p.big)
+        std::snprintf(name, cap, "knn_b16w_tile_kernel%s<%d, %d, %s>",
+                      ix->xt_state == TailCopy::Built && rp.tail_ok ? "_i8t" : "", p.km, l2,
+                      p.ib > 0 ? "true" : "false");
+    else       // (Route's values are the generic tile's kMode* arithmetic: Exact, Split, B16)
+        std::snprintf(name, cap, "knn_tile_topk_kernel<%d, %d, ..., %d, ...>", p.wr, p.wq, (int)rp.route);
     return KNN_OK;
 }
 
@@ -843,7 +835,7 @@ int knn_debug_i8tail(knn_index_t* ix, int* head, int* dpt, int64_t i0, int64_t n
     if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
     if (ix->multi) KNN_FAIL(KNN_EINVAL, "knn_debug_i8tail: single-device indexes only");
     IndexOp op(ix);
-    if (ix->xt_state != 1 || !ix->xt) KNN_FAIL(KNN_EINVAL, "the index has no int8 tail copy");
+    if (ix->xt_state != TailCopy::Built || !ix->xt) KNN_FAIL(KNN_EINVAL, "the index has no int8 tail copy");
     if (i0 < 0 || n < 0 || i0 + n > ix->ntotal) KNN_FAIL(KNN_EINVAL, "rows outside [0, ntotal)");
     if (head) *head = ix->xt_head;
     if (dpt) *dpt = ix->xt_dpt;

@@ -1,8 +1,8 @@
 // knn_index.h — internal state of one k-NN index and the helpers the C-ABI translation units
-// share (knn_capi.cpp: entry points; knn_plan.cpp: launch geometry and error-bound coefficients;
-// knn_search.cpp: the search paths; knn_io.cpp: the faiss file layout; knn_multi.cpp: one index
-// over several devices; knn_range.hip: range search; knn_filter.hip: filtered search;
-// knn_remove.hip: remove_ids).  Not part of the public ABI
+// share (knn_capi.cpp: entry points; knn_plan.h / knn_plan.cpp: the HIP-free route choice, launch
+// geometry and error-bound coefficients; knn_search.cpp: the search paths; knn_io.cpp: the faiss
+// file layout; knn_multi.cpp: one index over several devices; knn_range.hip: range search;
+// knn_filter.hip: filtered search; knn_remove.hip: remove_ids).  Not part of the public ABI
 // (include/imgrec_knn.h).
 //
 // Ownership: every device or page-locked allocation the index keeps is a DevBuf / PinBuf member
@@ -18,9 +18,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/imgrec_knn.h"
 #include "dev_buf.h"
 #include "knn_kernels.h"
+#include "knn_plan.h"      // (and with it include/imgrec_knn.h)
 #include "stream_fence.h"
 
 namespace imgrec {
@@ -97,52 +97,16 @@ struct HipStreams {
     static int fail(int e, const char* call) { return hip_result((hipError_t)e, call); }
 };
 
-// ---- launch geometry (knn_plan.cpp; DESIGN.md "Launch plan") ---------------------------------
-struct Plan {
-    int wr, wq, km, bm, bq;
-    int nqb, nq_pad, ntiles, nsplit, ncand, wgs;
-    bool big;                    // bf16 path: the 256 x 256-tile kernel (knn_b16w.hip)
-    int ib;                      // > 0: its packed-list form with ib split-local index bits
-};
-constexpr int64_t kQueryChunk = 8192;
-Plan make_plan(int64_t ntotal, int64_t nq, int k, int cus);
-Plan make_split_plan(int64_t ntotal, int64_t nq, int kc, int cus);
-Plan make_b16_plan(int64_t ntotal, int64_t nq, int k, int cus, int dpb);
-// The exact re-run of uncertified queries (inside the certificate tail kernel): the (2,1) tile
-// of make_plan (256 rows x 32 queries), planned on device for whatever count the certificate
-// leaves.
-constexpr int kFallbackWR = 2;                 // lists per row split = 2 * kFallbackWR
-int fallback_km(int k);
-int split_kc(int k);
-float split_coef(int dp);
-float rerank_coef(int dp);
-float b16_acc_coef(int dpb);
-// int8 tail of the 256 x 256 kernel (knn_b16w_tile_kernel_i8t): the accumulation coefficient of a
-// pass with `head` bf16 columns (knn_certify.h i8tail_e_ip), and the split column from the corpus's
-// per-block max |x| (nblk = dpb / 64 blocks): a multiple of 64, or -1 = the route is off
-float i8t_acc_coef(int head);
-int i8t_pick_head(const float* blkmax, int nblk);
-constexpr int kI8TMinTail = 512;               // tail columns below which the route is off
-// int8 small-batch pass (knn_i8.hip): batches of at most kI8MaxQ queries, K' = kB16Cand
-constexpr int kI8MaxQ = 8;
-float i8_acc_coef(int nblk);
-// wgpcu: int8 scan workgroups per CU (the split count is CUs x wgpcu); 0 = by batch size
-Plan make_i8_plan(int64_t ntotal, int64_t nq, int k, int cus, int wgpcu, int nblk);
-constexpr int kI8WGPCUDefault = 0;
-constexpr int kB16Cand = 64;                   // K': candidates the bf16 pass hands to the rerank
-int b16_km(int k);
-
 }  // namespace imgrec
 
 using imgrec::DevBuf;
 using imgrec::PinBuf;
 
-struct knn_index {
-    int d = 0, dp = 0, metric = KNN_METRIC_L2, device = 0, cus = 256;
-    // launch knobs read from the environment at creation (A/B and tests): the int8 scan's
-    // workgroups per CU (IMGREC_I8_WGPCU) and the merge's second level inside the rerank
-    // (IMGREC_MERGE_FUSE=0: off)
-    int i8_wgpcu = imgrec::kI8WGPCUDefault;
+// (IndexShape, knn_plan.h: d, dp, dpb, nblk8, cus, metric, mode, ntotal, ... — what choose_route reads)
+struct knn_index : imgrec::IndexShape {
+    int device = 0;
+    // launch knob read from the environment at creation (A/B and tests): the merge's second level
+    // inside the rerank (IMGREC_MERGE_FUSE=0: off)
     bool merge_fuse = true;
     bool chance_skip = true;    // IMGREC_CHANCE_SKIP=0: every query takes the first rerank
     // int8 batches of at most this many queries skip the merge and the first rerank: the
@@ -172,13 +136,11 @@ struct knn_index {
     // IMGREC_B16W_SHARED_BOUND=0: the 256 x 256 bf16 kernel's lists screen each on their own (no
     // shared per-query bound, TileArgs::sbound)
     bool shared_bound = true;
-    // IMGREC_B16W_I8TAIL=0: AUTO / i8 large batches stay on the pure bf16 256 x 256 kernel
-    bool i8tail = true;
     bool rerank_nw4 = false;    // IMGREC_RERANK_NW4=1: large batches rerank on 4-wave workgroups
     bool rerank_p1k = true;     // large batches rerank k rows first (IMGREC_RERANK_P1=0: 16)
     bool i8_fused_prep = true;  // int8 query prep inside the scan (IMGREC_I8_FUSED_PREP=0: own launch)
     bool merge_fuse1 = true;    // IMGREC_MERGE_FUSE=1: only level 2 in the rerank (0: neither)
-    int64_t ntotal = 0, cap = 0, id_offset = 0;
+    int64_t cap = 0, id_offset = 0;
     bool trained = true;
     DevBuf<float> xb;     // cap x dp
     DevBuf<float> xn;     // cap
@@ -195,8 +157,7 @@ struct knn_index {
     DevBuf<float> xts;       // cap: scale max|x_tail| / 127
     DevBuf<float4> xtm;      // cap: (|x_tail - s c|, |x_head - bf16(x_head)|, |x_tail|, |x_head|), rounded up
     DevBuf<float> xt_max;    // device: the four maxima of xtm (R_t, R_h, X_t, X_h)
-    int xt_state = 0;        // 0 = not decided yet (until reset), 1 = built, -1 = the index is not eligible
-    int xt_head = 0, xt_dpt = 0;
+    int xt_head = 0, xt_dpt = 0;     // (its state: IndexShape::xt_state)
     // the copy's first search is a trial: its certificate counts decide whether the index keeps the
     // route (search_locked); false again after reset
     bool xt_tried = false;
@@ -204,15 +165,12 @@ struct knn_index {
     DevBuf<int8_t> qt;       // a search's query tail codes, scales and inner-product bounds
     DevBuf<float> qts;
     DevBuf<float> q_eip;
-    int nblk8 = 0;           // 64-element blocks per row (d <= 4096)
     DevBuf<int8_t> q8;        // a search's two-level query codes
     DevBuf<float> q8s;       //   their scales
     DevBuf<float> q8r;       //   |q - q~| per query
     DevBuf<float> xn_max; // device scalar, max |x|^2 (refreshed when rows change)
     DevBuf<float> xr_max; // device scalar, max |x - bf16(x)|
-    int dpb = 0;             // bf16 row stride (elements)
-    bool split_ok = false, b16_ok = false, xn_max_stale = true;
-    int mode = KNN_SEARCH_AUTO;
+    bool xn_max_stale = true;
     int last_path = 0;       // knn_last_path
     int64_t last_split_queries = 0;   // queries of the last search on a candidate path
     hipStream_t stream = nullptr;     // the index's own stream (host-pointer entry points)
@@ -340,10 +298,10 @@ int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st);
 int ensure_split(knn_index* ix, hipStream_t st);
 int ensure_i8(knn_index* ix, hipStream_t st);
 // the int8 tail copy: decides the index's eligibility and split column once (a host wait for the
-// corpus statistics), builds the copy; xt_state says which.  use_i8tail: the route's conditions
-// that need no build (mode, knob, plan)
+// corpus statistics), builds the copy; xt_state says which.  drop_i8tail: the copy's only teardown,
+// leaving xt_state = next (the caller has drained the streams that read it)
 int ensure_i8tail(knn_index* ix, hipStream_t st);
-bool use_i8tail(const knn_index* ix, int64_t nq, int k);
+void drop_i8tail(knn_index* ix, imgrec::TailCopy next);
 int create_single(int d, int metric, int device, knn_index** out);
 void free_single(knn_index* ix);
 // knn_search.cpp
@@ -354,8 +312,6 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
 int timed_begin(knn_index* ix, hipStream_t st, hipEvent_t* e1);
 int read_search_stats(knn_index* ix, int64_t* split_q, int64_t* fallback_q, int64_t* first_fail,
                       float* ratio);
-bool use_b16(const knn_index* ix, int64_t nq, int k);
-bool use_i8(const knn_index* ix, int64_t nq, int k);
 // knn_largek.hip
 int largek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                   hipStream_t st);
@@ -373,7 +329,6 @@ int largek_fallbacks(knn_index* ix, int64_t* n);
 hipError_t launch_merge_large(const float* cD, const int64_t* cI, int nlists, int64_t nq, int kin,
                               int64_t sd, int64_t si, int k, int metric, float* D, int64_t* I,
                               hipStream_t st);
-bool use_split(const knn_index* ix, int64_t nq, int k);
 // knn_hugek.hip: k > KNN_MAX_K_LARGE — every (query, row) key, a segmented sort per query
 int hugek_search(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                  hipStream_t st);

@@ -19,13 +19,6 @@
 
 namespace imgrec {
 
-namespace {
-
-// 1 = L2, 0 = inner product (cosine rows are normalised): the kernels' metric argument
-int kmetric_of(const knn_index* ix) { return ix->metric == KNN_METRIC_L2 ? 1 : 0; }
-
-}  // namespace
-
 // Timing events around the dominant (fused) kernel launch of a chunk.
 int timed_begin(knn_index* ix, hipStream_t st, hipEvent_t* e1) {
     *e1 = nullptr;
@@ -45,9 +38,21 @@ int timed_begin(knn_index* ix, hipStream_t st, hipEvent_t* e1) {
 
 namespace {
 
-// Exact fp32 path over nq padded queries (qpad holds make_plan(nq).nq_pad zero-padded rows).
-int exact_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,
-                int64_t* I, hipStream_t st, bool timed) {
+// 1 = L2, 0 = inner product (cosine rows are normalised): the kernels' metric argument
+int kmetric_of(const knn_index* ix) { return ix->metric == KNN_METRIC_L2 ? 1 : 0; }
+
+// A chunk's dominant launch between the two events of a timing pair (knn_kernel_time: one a chunk).
+#define KNN_TIMED(ix, st, launch)                                          \
+    do {                                                                   \
+        hipEvent_t e1_ = nullptr;                                          \
+        if (const int rc_ = timed_begin(ix, st, &e1_)) return rc_;         \
+        KNN_HIP(launch);                                                   \
+        if (e1_) KNN_HIP(hipEventRecord(e1_, st));                         \
+    } while (0)
+
+// Exact fp32 path over nq padded queries (qpad holds p.nq_pad zero-padded rows).
+int exact_chunk(knn_index* ix, const Plan& p, const float* qpad, const float* qnorm, int64_t nq, int k,
+                float* D, int64_t* I, hipStream_t st) {
     const int kmetric = kmetric_of(ix);
     int rc;
     if (stream_lists_ok(ix, nq)) {
@@ -58,15 +63,11 @@ int exact_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
         const size_t nc = (size_t)sp * KNN_MAX_K;
         if ((rc = ix->cand_d.reserve((size_t)nq * nc)) != KNN_OK) return rc;
         if ((rc = ix->cand_i.reserve((size_t)nq * nc)) != KNN_OK) return rc;
-        hipEvent_t e1 = nullptr;
-        if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
-        KNN_HIP(launch_stream_lists(ix, qpad, qnorm, nq, kmetric, sp, ix->cand_d, ix->cand_i, st));
-        if (e1) KNN_HIP(hipEventRecord(e1, st));
+        KNN_TIMED(ix, st, launch_stream_lists(ix, qpad, qnorm, nq, kmetric, sp, ix->cand_d, ix->cand_i, st));
         KNN_HIP(launch_merge(ix->cand_d, ix->cand_i, nq, sp, KNN_MAX_K, (int64_t)nc, KNN_MAX_K, k,
                              kmetric, 0, D, I, st));
         return KNN_OK;
     }
-    const Plan p = make_plan(ix->ntotal, nq, k, ix->cus);
     if ((rc = ix->cand_d.reserve((size_t)nq * p.ncand)) != KNN_OK) return rc;
     if ((rc = ix->cand_i.reserve((size_t)nq * p.ncand)) != KNN_OK) return rc;
     TileArgs a{};
@@ -75,10 +76,7 @@ int exact_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
     a.qp = qpad; a.qnorm = qnorm; a.nq = (int)nq; a.metric = kmetric;
     a.ntiles = p.ntiles; a.nsplit = p.nsplit; a.nqb = p.nqb; a.id_offset = ix->id_offset;
     a.cand_d = ix->cand_d; a.cand_i = ix->cand_i; a.ncand = p.ncand; a.mode = kModeF32;
-    hipEvent_t e1 = nullptr;
-    if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
-    KNN_HIP(launch_tile_topk(a, st));
-    if (e1) KNN_HIP(hipEventRecord(e1, st));
+    KNN_TIMED(ix, st, launch_tile_topk(a, st));
     KNN_HIP(launch_merge(ix->cand_d, ix->cand_i, nq, p.ncand / p.km, p.km, p.ncand, p.km, k,
                          kmetric, 0, D, I, st));
     return KNN_OK;
@@ -321,14 +319,15 @@ bool stream_capturing(hipStream_t st) {
 // The int8 tail of a chunk that takes the route (search_locked, ahead of the fused query prep):
 // the copy is built if this is its first search, the maxima the prep reads are refreshed, the
 // query-side buffers grown.  tp->codes stays NULL when the chunk stays on the pure bf16 pass.
-int i8tail_prep(knn_index* ix, const Plan& p, int64_t nq, int k, hipStream_t st, I8TailPrep* tp) {
+int i8tail_prep(knn_index* ix, const RoutePlan& rp, hipStream_t st, I8TailPrep* tp) {
     *tp = I8TailPrep{};
-    if (!use_i8tail(ix, nq, k)) return KNN_OK;
+    if (!rp.tail_ok) return KNN_OK;
+    const Plan& p = rp.plan;
     // building the copy waits on the host, which a capturing stream does not allow: such a search
     // runs the bf16 pass and leaves the build to the next search outside a capture
-    if (ix->xt_state == 0 && stream_capturing(st)) return KNN_OK;
+    if (ix->xt_state == TailCopy::Undecided && stream_capturing(st)) return KNN_OK;
     int rc;
-    if ((rc = ensure_i8tail(ix, st)) != KNN_OK || ix->xt_state != 1) return rc;
+    if ((rc = ensure_i8tail(ix, st)) != KNN_OK || ix->xt_state != TailCopy::Built) return rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
     if ((rc = ix->qt.reserve((size_t)p.nq_pad * ix->xt_dpt)) != KNN_OK) return rc;
     if ((rc = ix->qts.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
@@ -356,18 +355,16 @@ int i8tail_trial(knn_index* ix, int64_t nq, hipStream_t st) {
     ix->xt_tried = true;
     const int64_t reruns = acc[0];
     if (reruns * 32 <= nq) return KNN_OK;
-    ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();      // (st is drained: nothing reads them)
-    ix->xt_state = -1;
+    drop_i8tail(ix, TailCopy::Ineligible);                  // (st is drained: nothing reads the copy)
     return KNN_OK;
 }
 
 // bf16 candidates (one bf16 MFMA per product) + exact fp32 rerank of K' = 64 + certificate.
 // i8t: the 256 x 256 kernel's int8-tail sibling (the prep wrote the query's tail codes and e_ip).
-int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,
-              int64_t* I, hipStream_t st, bool timed, bool q_ready, bool first, bool i8t) {
+int b16_chunk(knn_index* ix, const Plan& p, const float* qpad, const float* qnorm, int64_t nq, int k,
+              float* D, int64_t* I, hipStream_t st, bool q_ready, bool first, bool i8t) {
     const int kmetric = kmetric_of(ix);
     const int kc = kB16Cand;
-    const Plan p = make_b16_plan(ix->ntotal, nq, k, ix->cus, ix->dpb);
     const int km = p.km;
     int rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
@@ -389,14 +386,12 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
     a.ib = p.big ? p.ib : 0;
     a.sbound = sb.rec;
     if (i8t) {
-        if (!p.big || !q_ready || ix->xt_state != 1) KNN_FAIL(KNN_EINVAL, "int8 tail without its query prep");
+        if (!p.big || !q_ready || ix->xt_state != TailCopy::Built)
+            KNN_FAIL(KNN_EINVAL, "int8 tail without its query prep");
         a.xt = ix->xt; a.xts = ix->xts; a.qt = ix->qt; a.qts = ix->qts;
         a.t_head = ix->xt_head; a.t_dpt = ix->xt_dpt;
     }
-    hipEvent_t e1 = nullptr;
-    if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
-    KNN_HIP(p.big ? launch_b16_big(a, st) : launch_tile_topk(a, st));
-    if (e1) KNN_HIP(hipEventRecord(e1, st));
+    KNN_TIMED(ix, st, p.big ? launch_b16_big(a, st) : launch_tile_topk(a, st));
     const int nlists = p.ncand / km;
     RerankArgs r = rerank_args(ix, kModeBF16, qpad, qnorm, nq, k, kc, D, I);
     r.c_split = b16_acc_coef(ix->dpb);
@@ -414,11 +409,10 @@ int b16_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, 
 
 // Block-scaled int8 candidates (int8 dot4 products, batches of <= kI8MaxQ queries) + exact fp32
 // rerank of K' = 64 + certificate: the bf16 path's chain with the int8 copy's bound.
-int i8_chunk(knn_index* ix, const float* qraw, const float* qpad, const float* qnorm, int64_t nq,
-             int k, float* D, int64_t* I, hipStream_t st, bool timed, bool first) {
+int i8_chunk(knn_index* ix, const Plan& p, const float* qraw, const float* qpad, const float* qnorm,
+             int64_t nq, int k, float* D, int64_t* I, hipStream_t st, bool first) {
     const int kmetric = kmetric_of(ix);
     const int kc = kB16Cand;
-    const Plan p = make_i8_plan(ix->ntotal, nq, k, ix->cus, ix->i8_wgpcu, ix->nblk8);
     // direct: no merge, no rerank launch — the certificate tail reranks every query's list entries
     // under its prefix limit (RerankArgs::direct); the scan zeroes the tail's claim counters and
     // (raw: <= 4 queries) writes its 16 lane lists per split unfolded
@@ -470,10 +464,7 @@ int i8_chunk(knn_index* ix, const float* qraw, const float* qpad, const float* q
         if ((rc = ix->heads.reserve((size_t)nq * p.nsplit)) != KNN_OK) return rc;
         a.heads = ix->heads;
     }
-    hipEvent_t e1 = nullptr;
-    if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
-    KNN_HIP(launch_i8_scan(a, st));
-    if (e1) KNN_HIP(hipEventRecord(e1, st));
+    KNN_TIMED(ix, st, launch_i8_scan(a, st));
     const int nlists = p.nsplit;
     RerankArgs r = rerank_args(ix, kModeI8, qpad, qnorm, nq, k, kc, D, I);
     r.c_split = i8_acc_coef(ix->nblk8);
@@ -492,11 +483,10 @@ int i8_chunk(knn_index* ix, const float* qraw, const float* qpad, const float* q
 }
 
 // Split-bf16 candidates + exact rerank + certificate.
-int split_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq, int k, float* D,
-                int64_t* I, hipStream_t st, bool timed, bool first) {
+int split_chunk(knn_index* ix, const Plan& p, const float* qpad, const float* qnorm, int64_t nq, int k,
+                float* D, int64_t* I, hipStream_t st, bool first) {
     const int kmetric = kmetric_of(ix);
-    const int kc = split_kc(k);
-    const Plan p = make_split_plan(ix->ntotal, nq, kc, ix->cus);
+    const int kc = p.km;                     // split_kc(k)
     int rc;
     if ((rc = ensure_split(ix, st)) != KNN_OK) return rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
@@ -512,10 +502,7 @@ int split_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
     a.id_offset = ix->id_offset; a.cand_d = ix->cand_d; a.cand_i = ix->cand_i;
     a.ncand = p.ncand; a.mode = kModeSplit;
     a.wb = kSplitWB; a.sbk = kSplitBK;
-    hipEvent_t e1 = nullptr;
-    if (timed && (rc = timed_begin(ix, st, &e1)) != KNN_OK) return rc;
-    KNN_HIP(launch_tile_topk(a, st));
-    if (e1) KNN_HIP(hipEventRecord(e1, st));
+    KNN_TIMED(ix, st, launch_tile_topk(a, st));
     // global top-K' approximate candidates, raw ascending keys (merge in its L2 convention)
     KNN_HIP(launch_merge(ix->cand_d, ix->cand_i, nq, p.ncand / kc, kc, p.ncand, kc, kc, 1, 0,
                          ix->cand2_d, ix->cand2_i, st));
@@ -528,65 +515,6 @@ int split_chunk(knn_index* ix, const float* qpad, const float* qnorm, int64_t nq
 }
 
 }  // namespace
-
-// AUTO: the bf16 path at every corpus size.  Large batches are matrix-bound (bf16 MFMA vs fp32
-// MFMA), small ones HBM-bound (the bf16 copy streams half the bytes), and on small corpora the
-// exact kernel has a latency floor of its own: one 256-row tile's whole depth of fp32 MFMAs per
-// workgroup, ~0.16 ms from 1000 rows up, against the candidate path's ~0.05-0.1 ms
-// (profiles/r03/small_corpora/: 1000-131072 rows x nq 9-1024, bf16 1.8-2.8x faster).
-bool use_b16(const knn_index* ix, int64_t nq, int k) {
-    if (!ix->b16_ok || k > KNN_MAX_K) return false;
-    if (ix->mode == KNN_SEARCH_BF16) return true;
-    // (I8 mode: batches the int8 path does not take are served as AUTO serves them)
-    return ix->mode == KNN_SEARCH_AUTO || ix->mode == KNN_SEARCH_I8;
-}
-
-// AUTO: batches of <= kI8AutoQ queries at every corpus size (the int8 copy streams about half of
-// the bf16 copy's bytes; its dot products grow with the batch: nq <= 4 is HBM-bound, nq = 5-8
-// VALU-bound and still faster than the bf16 pass; one query on 1000-65536 rows 0.05-0.075 ms
-// against the exact kernel's 0.18-0.22, profiles/r03/small_corpora/)
-// A row's 16-lane group in the scan has one lane per 64-element block, so narrow rows leave most
-// lanes idle (d = 128: 2 of 16).  One or two queries stay HBM-bound at every width since the
-// rows are compact (round 4): one query on 1M rows, int8 against bf16, 0.133 / 0.143 ms at
-// d = 64, 0.134 / 0.154 at 128, 0.137 / 0.183 at 256, 0.140 / 0.221 at 384, 0.140 / 0.247 at 512
-// (profiles/r05/small_d/), so they take the int8 path at any width.  Larger batches multiply the
-// dot products per byte: below kI8MinBlocks blocks they take it only while the copy is small
-// enough (<= 64 MB, ~10 us of streaming) for the fixed costs to decide.
-constexpr int kI8AutoQ = 8;
-constexpr int kI8MinBlocks = 8;
-// 5-8 queries run the scan's 8-query instance, VALU-bound: its time steps with the blocks per
-// lane (NBI = ceil(blocks / 16)), the bf16 pass's grows with d.  One box, 1M rows
-// (profiles/r05/modes_nq/, small_d/): 8 queries int8 / bf16 0.355 / 0.326 ms at 12 blocks,
-// 0.339 / 0.397 at 16, 0.530 / 0.496 at 20, 0.585 / 0.679 at 31 — the int8 route at 14-16 blocks
-// and from 23
-bool i8_wins_8q(int nblk) { return (nblk >= 14 && nblk <= 16) || nblk >= 23; }
-constexpr int64_t kI8SmallCopyBytes = 64ll << 20;
-bool use_i8(const knn_index* ix, int64_t nq, int k) {
-    if (ix->nblk8 <= 0 || k > KNN_MAX_K || nq > kI8MaxQ) return false;
-    if (ix->mode == KNN_SEARCH_I8) return true;
-    if (ix->mode != KNN_SEARCH_AUTO || nq > kI8AutoQ) return false;
-    const int64_t i8_row = i8_row_bytes(ix->nblk8) + 4 * ix->nblk8;
-    const bool wide_enough = nq <= 2 ? true : nq <= 4 ? ix->nblk8 >= kI8MinBlocks : i8_wins_8q(ix->nblk8);
-    return !ix->b16_ok || wide_enough || ix->ntotal * i8_row <= kI8SmallCopyBytes;
-}
-
-// The 256 x 256 kernel's int8 tail: AUTO and the i8 mode, on the big plan, unless the knob turned it
-// off at creation or the index turned out not to be eligible (ensure_i8tail; dpb <= 4096: the fused
-// query prep writes the query side).  search_mode = "bf16" stays the pure bf16 pass.
-bool use_i8tail(const knn_index* ix, int64_t nq, int k) {
-    if (!ix->i8tail || ix->xt_state < 0 || ix->dpb > 4096 || ix->ntotal <= 0) return false;
-    if (ix->mode != KNN_SEARCH_AUTO && ix->mode != KNN_SEARCH_I8) return false;
-    if (use_i8(ix, nq, k) || !use_b16(ix, nq, k)) return false;
-    return make_b16_plan(ix->ntotal, nq, k, ix->cus, ix->dpb).big;
-}
-
-bool use_split(const knn_index* ix, int64_t nq, int k) {
-    if (!ix->split_ok || ix->mode == KNN_SEARCH_EXACT || split_kc(k) == 0) return false;
-    if (ix->mode == KNN_SEARCH_SPLIT) return true;
-    // auto (when the bf16 path is unavailable): batches the (1,4) plan covers, corpora with
-    // enough rows to amortise the rerank
-    return (ix->mode == KNN_SEARCH_AUTO || ix->mode == KNN_SEARCH_I8) && nq > 128 && ix->ntotal >= 16384;
-}
 
 int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, int64_t* I,
                   hipStream_t st) {
@@ -606,63 +534,51 @@ int search_locked(knn_index* ix, const float* q, int64_t nq, int k, float* D, in
     bool first_cand = true, any_i8t = false;
     for (int64_t c0 = 0; c0 < nq; c0 += kQueryChunk) {
         const int64_t cn = std::min(kQueryChunk, nq - c0);
-        const bool i8 = use_i8(ix, cn, k);
-        const bool b16 = !i8 && use_b16(ix, cn, k);
-        const bool split = !i8 && !b16 && use_split(ix, cn, k);
-        // padding: the query tile of the plan this chunk will run (and the exact re-run's 32)
-        const Plan p = i8 ? make_i8_plan(ix->ntotal, cn, k, ix->cus, ix->i8_wgpcu, ix->nblk8)
-                     : b16 ? make_b16_plan(ix->ntotal, cn, k, ix->cus, ix->dpb)
-                     : split ? make_split_plan(ix->ntotal, cn, split_kc(k), ix->cus)
-                             : make_plan(ix->ntotal, cn, k, ix->cus);
+        // the chunk's one decision; padding: the query tile of its plan (and the exact re-run's 32)
+        const RoutePlan rp = choose_route(*ix, cn, k);
+        const Plan& p = rp.plan;
+        const bool i8 = rp.route == Route::I8, b16 = rp.route == Route::B16;
         const int64_t nq_pad = p.nq_pad;
         int rc;
-        if (c0 == 0) ix->last_path = i8 ? 3 : (b16 ? 2 : (split ? 1 : 0));
+        if (c0 == 0) ix->last_path = (int)rp.route;
         if ((rc = ix->qpad.reserve((size_t)nq_pad * ix->dp)) != KNN_OK) return rc;
         if ((rc = ix->qnorm.reserve((size_t)nq_pad)) != KNN_OK) return rc;
-        bool q_ready = false, i8t = false;
+        bool i8t = false;
         // fused query prep: fp32 padded rows + norms + bf16 + residuals, or for the int8 path
         // the same rows and norms + the two-level int8 codes (one short pass instead of
         // rows_ingest's latency-bound row loop and a second launch)
         // (the int8 path's prep runs inside its scan unless IMGREC_I8_FUSED_PREP=0: nq_pad = cn)
         const bool i8_fused = i8 && ix->i8_fused_prep && nq_pad == cn && cn <= 4;
-        if (i8) {
-            if ((rc = ix->q8r.reserve((size_t)cn)) != KNN_OK) return rc;
-        }
-        if (i8_fused) {
-            q_ready = true;
-        } else if (i8) {
+        const bool q_ready = b16 && ix->dpb <= 4096;     // b16_chunk: the prep here wrote qb16 / q_resid
+        if (i8 && (rc = ix->q8r.reserve((size_t)cn)) != KNN_OK) return rc;
+        if (i8 && !i8_fused) {
             if ((rc = ix->q8.reserve((size_t)cn * ix->nblk8 * 128)) != KNN_OK) return rc;
             if ((rc = ix->q8s.reserve((size_t)cn * ix->nblk8 * 2)) != KNN_OK) return rc;
             KNN_HIP(launch_i8_query_prep(q + c0 * ix->d, cn, ix->d, ix->dp, nq_pad, normalize,
                                          ix->nblk8, ix->qpad, ix->qnorm, ix->q8, ix->q8s, ix->q8r, st));
-            q_ready = true;
-        } else if (b16 && ix->dpb <= 4096) {
+        } else if (q_ready) {
             if ((rc = ix->qb16.reserve((size_t)nq_pad * ix->dpb)) != KNN_OK) return rc;
             if ((rc = ix->q_resid.reserve((size_t)nq_pad)) != KNN_OK) return rc;
             I8TailPrep tp;
-            if ((rc = i8tail_prep(ix, p, cn, k, st, &tp)) != KNN_OK) return rc;
+            if ((rc = i8tail_prep(ix, rp, st, &tp)) != KNN_OK) return rc;
             i8t = tp.codes != nullptr;
             SharedBoundPrep sb;
             if ((rc = shared_bound_prep(ix, p, ix->qnorm, st, &sb)) != KNN_OK) return rc;
             KNN_HIP(launch_query_prep_b16(q + c0 * ix->d, cn, ix->d, ix->dp, ix->dpb, nq_pad,
                                           normalize, ix->qpad, ix->qnorm, ix->qb16, ix->q_resid, st,
                                           &sb, &tp));
-            q_ready = true;
-        } else {
+        } else if (!i8) {
             KNN_HIP(launch_rows_ingest(q + c0 * ix->d, cn, ix->d, ix->dp, nq_pad, normalize,
                                        ix->qpad, ix->qnorm, st));
         }
         float* Dc = D + c0 * k;
         int64_t* Ic = I + c0 * k;
-        if (i8 || b16 || split) {
-            rc = i8 ? i8_chunk(ix, i8_fused ? q + c0 * ix->d : nullptr, ix->qpad, ix->qnorm, cn, k,
-                               Dc, Ic, st, true, first_cand)
-               : b16 ? b16_chunk(ix, ix->qpad, ix->qnorm, cn, k, Dc, Ic, st, true, q_ready, first_cand, i8t)
-                     : split_chunk(ix, ix->qpad, ix->qnorm, cn, k, Dc, Ic, st, true, first_cand);
-            first_cand = false;
-        } else {
-            rc = exact_chunk(ix, ix->qpad, ix->qnorm, cn, k, Dc, Ic, st, true);
-        }
+        const float *qp = ix->qpad, *qn = ix->qnorm;
+        rc = i8 ? i8_chunk(ix, p, i8_fused ? q + c0 * ix->d : nullptr, qp, qn, cn, k, Dc, Ic, st, first_cand)
+           : b16 ? b16_chunk(ix, p, qp, qn, cn, k, Dc, Ic, st, q_ready, first_cand, i8t)
+           : rp.route == Route::Split ? split_chunk(ix, p, qp, qn, cn, k, Dc, Ic, st, first_cand)
+                                      : exact_chunk(ix, p, qp, qn, cn, k, Dc, Ic, st);
+        first_cand = first_cand && rp.route == Route::Exact;
         if (rc != KNN_OK) return rc;
         any_i8t = any_i8t || i8t;
     }

@@ -106,6 +106,7 @@ SIGNATURES = {
     "knn_search_stats2": (_i, [_vp, _pi64, _pi64, _pi64, _pf]),
     "knn_last_path": (_i, [_vp]),
     "knn_debug_i8tail": (_i, [_vp, _pi, _pi, _i64, _i64, _vp, _vp, _vp]),
+    "knn_debug_i8tail_rows": (_i, [_vp, _i64, _i64, _pi, _vp]),
     "knn_large_k_fallbacks": (_i, [_vp, C.POINTER(_i64)]),
     "knn_last_error": (C.c_char_p, []),
     "knn_version": (C.c_char_p, []),

@@ -62,6 +62,7 @@
 #include <type_traits>
 
 #include "knn_kernels.h"
+#include "knn_plan.h"
 #include "lds_dma.h"
 #include "wave_ops.h"
 
@@ -238,24 +239,34 @@ __device__ unsigned long long g_b16w_stamps[8 * 256];
 __device__ unsigned long long g_b16w_wg[2 * 1024];
 #define B16W_STAMP(slot) do { if (stamp_on && lane == 0) { \
     unsigned long long v_ = __builtin_amdgcn_s_memtime(); g_b16w_stamps[wave * 256 + (slot)] = v_; } } while (0)
+// per workgroup (blockIdx.x < 1024), wave 0's sums over its tiles' stage loops, (shader cycles,
+// 100 MHz ticks, stages) for the int8 tail stages, then for the bf16 stages: one s_memtime and one
+// s_memrealtime before and after each loop (tools/i8joint_stamps.py: cycles per stage, clock)
+__device__ unsigned long long g_b16w_loop[6 * 1024];
+#define B16W_LOOP_BEGIN() const unsigned long long lc0_ = __builtin_amdgcn_s_memtime(), \
+                                                   lr0_ = __builtin_amdgcn_s_memrealtime()
+#define B16W_LOOP_END(kind, n) do { lp_cyc[kind] += __builtin_amdgcn_s_memtime() - lc0_; \
+    lp_rt[kind] += __builtin_amdgcn_s_memrealtime() - lr0_; lp_n[kind] += (unsigned long long)(n); } while (0)
 #else
 #define B16W_STAMP(slot) do {} while (0)
+#define B16W_LOOP_BEGIN() do {} while (0)
+#define B16W_LOOP_END(kind, n) do {} while (0)
 #endif
 
 // PACK: one u32 per list entry (see ord_bits), ib = index bits (host: every split-local row index
 // t * 256 + tile row fits); otherwise separate key / label lists (any corpus size).
 //
-// I8T (knn_b16w_tile_kernel_i8t, DESIGN.md "int8 tail"): a tile's first ta.nst_t stages are 128
-// int8 deep (the tail copy's codes: the same 128 B per row, the same two k-steps of four 16-B chunks
-// and the same fragment addresses, on v_mfma_i32_16x16x64_i8 into the accumulator registers as
-// int32), then the registers are folded in place to fp32 (x row scale x query scale) and the
-// ta.nst_h bf16 stages of the rows' first 64 ta.nst_h columns accumulate on top.
+// I8T (knn_b16w_tile_kernel_i8t, DESIGN.md "int8 tail"): xh, qh and dw carry the joint rows of the
+// tail copy — a row is its tail codes, then its bf16 head, dw words in all — so a tile's stage s
+// reads bytes [128 s, 128 s + 128) of every row and query, exactly as the bf16 kernel does.  The
+// first ta.nst_t stages are 128 int8 deep (the same 128 B per row, the same two k-steps of four
+// 16-B chunks and the same fragment addresses, on v_mfma_i32_16x16x64_i8 into the accumulator
+// registers as int32), then the registers are folded in place to fp32 (x row scale x query scale)
+// and the remaining bf16 stages of the rows' head columns accumulate on top.
 struct I8TailArgs {
-    const uint32_t* xt = nullptr;    // rows' tail codes, dwt words per row
     const float* xts = nullptr;      // per-row scale
-    const uint32_t* qt = nullptr;    // queries' tail codes, dwt words per padded query
     const float* qts = nullptr;      // per-query scale
-    int dwt = 0, nst_t = 0, nst_h = 0;
+    int nst_t = 0;                   // tail stages of a joint row
 };
 
 template <int KM, int L2, bool PACK>
@@ -288,35 +299,35 @@ knn_b16w_tile_kernel_i8t(const uint32_t* __restrict__ xh, const float* __restric
 hipError_t launch_b16_big(const TileArgs& a, hipStream_t st) {
     if (a.wr != 2 || a.wq != 4 || a.dp % kBKW != 0 || a.nsplit < 1) return hipErrorInvalidValue;
     // the lane offsets are 32-bit: a tile's last group sits (kGPT - 1) * nsplit groups past its first
-    // (int8 tail: the same for the tail copy's row stride)
     const auto off_ok = [&](int64_t row_bytes) {
         return ((int64_t)(kGPT - 1) * a.nsplit * kRPP + kBQ) * row_bytes + 8192 < ((int64_t)1 << 32);
     };
     if (!off_ok((int64_t)a.dp * 4)) return hipErrorInvalidValue;
     const bool i8t = a.xt != nullptr;
     I8TailArgs ta;
-    if (i8t) {
-        // the head is whole 64-column stages inside the bf16 rows, the tail whole 128-column stages
-        if (a.t_head < 0 || a.t_head % 64 != 0 || a.t_head > 2 * a.dp || a.t_dpt < 128 || a.t_dpt % 128 != 0 ||
-            !a.xts || !a.qt || !a.qts || !off_ok(a.t_dpt))
-            return hipErrorInvalidValue;
-        ta.xt = reinterpret_cast<const uint32_t*>(a.xt);
-        ta.xts = a.xts;
-        ta.qt = reinterpret_cast<const uint32_t*>(a.qt);
-        ta.qts = a.qts;
-        ta.dwt = a.t_dpt / 4;
-        ta.nst_t = a.t_dpt / 128;
-        ta.nst_h = a.t_head / 64;
-    }
     const dim3 grid((unsigned)(a.nqb * a.nsplit)), block(kNW * 64);
     const uint32_t* xh = reinterpret_cast<const uint32_t*>(a.xb);
     const uint32_t* qh = reinterpret_cast<const uint32_t*>(a.qp);
+    int dw = a.dp;
+    if (i8t) {
+        // the head is whole 64-column stages inside the bf16 rows, the tail whole 128-column stages;
+        // the kernel reads both from the joint rows (i8t_joint_row_bytes) at one stride
+        if (a.t_head < 0 || a.t_head % 64 != 0 || a.t_head > 2 * a.dp || a.t_dpt < 128 || a.t_dpt % 128 != 0 ||
+            !a.xts || !a.qt || !a.qts || !off_ok(i8t_joint_row_bytes(a.t_head, a.t_dpt)))
+            return hipErrorInvalidValue;
+        xh = reinterpret_cast<const uint32_t*>(a.xt);
+        qh = reinterpret_cast<const uint32_t*>(a.qt);
+        dw = i8t_joint_row_bytes(a.t_head, a.t_dpt) / 4;
+        ta.xts = a.xts;
+        ta.qts = a.qts;
+        ta.nst_t = i8t_tail_stages(a.t_dpt);
+    }
     if (a.ib < 0 || a.ib > kB16PackMaxIB) return hipErrorInvalidValue;
 #define IMGREC_LAUNCH_B16W(KMV, L2V, PK)                                                             \
     do {                                                                                             \
         if (i8t)                                                                                     \
             hipLaunchKernelGGL((knn_b16w_tile_kernel_i8t<KMV, L2V, PK>), grid, block, 0, st, xh,    \
-                               a.xnorm, a.nrows, a.dp, qh, a.qnorm, a.nq, a.nsplit, a.nqb,           \
+                               a.xnorm, a.nrows, dw, qh, a.qnorm, a.nq, a.nsplit, a.nqb,             \
                                a.id_offset, a.cand_d, a.cand_i, a.ncand, a.ib, a.sbound, ta);        \
         else                                                                                         \
             hipLaunchKernelGGL((knn_b16w_tile_kernel<KMV, L2V, PK>), grid, block, 0, st, xh,        \
@@ -346,5 +357,8 @@ extern "C" int knn_b16w_stamps_read(unsigned long long* host) {
 }
 extern "C" int knn_b16w_wg_read(unsigned long long* host) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(imgrec::g_b16w_wg), sizeof(imgrec::g_b16w_wg));
+}
+extern "C" int knn_b16w_loop_read(unsigned long long* host) {
+    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(imgrec::g_b16w_loop), sizeof(imgrec::g_b16w_loop));
 }
 #endif

@@ -15,6 +15,8 @@
 #ifdef IMGREC_B16_STAMPS
     const int wg = blockIdx.x;
     if (threadIdx.x == 0 && wg < 1024) g_b16w_wg[2 * wg] = __builtin_amdgcn_s_memrealtime();
+    // stage-loop sums of this wave (B16W_LOOP_BEGIN / _END): [0] int8 tail stages, [1] bf16 stages
+    unsigned long long lp_cyc[2] = {0, 0}, lp_rt[2] = {0, 0}, lp_n[2] = {0, 0};
 #endif
     const int wgid = xcd_wgid();
     constexpr int kG = 4;
@@ -76,31 +78,15 @@
     const int pbase = (isA ? wave : wave - 4) * kLPW;
     const int prow = lane / kCPR, pchk = lane % kCPR;
     static_assert(kRPP == 8 && kRPB == 2 && kLPW % 2 == 0, "piece offset form");
-#if B16W_I8T
-    // (I8T: the head and the tail copy have different row strides, so a stage's issue works the two
-    // bases out from the lane for its stride instead of keeping two sets)
-    auto vpar_of = [&](int e, int words) {
-        // (from the lane anew at every issue: the empty asm keeps the compiler from hoisting the four
-        // values back into registers for the whole launch)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int prow = ln / kCPR, pchk = ln % kCPR;
-#else
+    // (I8T: xh, qh and dw are the joint rows — tail codes, then the bf16 head — so one stride serves
+    // every stage and the offsets are the bf16 kernel's)
     uint32_t vpar[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-#endif
         const int P = pbase + e, r = P * kRPP + prow;
         const int srow = isA ? P * nsplit * kRPP + prow : r;
-#if B16W_I8T
-        return (uint32_t)srow * (uint32_t)(words * 4) + 16u * (uint32_t)(pchk ^ ((r / kRPB) % kCPR));
-    };
-    uint32_t vpar[2] = {0u, 0u};
-    if constexpr (!I8T) { vpar[0] = vpar_of(0, dw); vpar[1] = vpar_of(1, dw); }
-#else
         vpar[e] = (uint32_t)srow * (uint32_t)(dw * 4) + 16u * (uint32_t)(pchk ^ ((r / kRPB) % kCPR));
     }
-#endif
     const uint32_t kPS = (uint32_t)((isA ? nsplit : 1) * kRPP * dw * 4);
     auto voff_of = [&](int j) {
         return vpar[j & 1] + (uint32_t)(j & ~1) * kPS - 1024u * (uint32_t)(j & 3);
@@ -149,58 +135,35 @@
         dma2_agent(wrec, smem0 + (uint32_t)(kRecOff + wave * (kQW * kSBWords * 4)), (uint32_t)lane * 16u);
     };
 
-#if B16W_I8T
-    // stages per tile: I8T runs nst_t tail stages, then nst_h head stages
-    const int nst_t = I8T ? ta.nst_t : 0;
-    const int nst = I8T ? ta.nst_t + ta.nst_h : dw / kBKW;
-#else
+    // stages per tile (I8T: a joint row's first nst_t stages are its tail codes, the rest its head)
     const int nst = dw / kBKW;
+#if B16W_I8T
+    const int nst_t = ta.nst_t;
 #endif
     const int total = (t1 - t0) * nst;
     const uint32_t* qblk = qh + (size_t)qb * kBQ * dw;
-#if B16W_I8T
-    const uint32_t* qblk_t = I8T ? ta.qt + (size_t)qb * kBQ * ta.dwt : nullptr;
-#endif
 
     int c_it = t0, c_is = 0;
     const uint32_t* c_tile = isA ? xh + (size_t)trow(t0, 0) * dw : qblk;
-#if B16W_I8T
-    const uint32_t* c_tile_t = !I8T ? nullptr : isA ? ta.xt + (size_t)trow(t0, 0) * ta.dwt : qblk_t;
-#endif
     int c_ng = (isA && t0 == t1 - 1) ? cnt - t0 * kGPT : kGPT;
     auto issue = [&](int g) __attribute__((always_inline)) {
 #if B16W_I8T
-        // (I8T: a tail stage reads the tail copy, at its stride; tl is wave-uniform)
-        const bool tl = I8T && c_is < nst_t;
-        const uint32_t* src;
-        uint32_t vp0 = 0u, vp1 = 0u, ps = 0u;
-        if constexpr (I8T) {
-            const int rw = tl ? ta.dwt : dw;
-            src = tl ? c_tile_t + c_is * kBKW : c_tile + (c_is - nst_t) * kBKW;
-            vp0 = vpar_of(0, rw);
-            vp1 = vpar_of(1, rw);
-            ps = (uint32_t)((isA ? nsplit : 1) * kRPP * rw * 4);
-        } else {
-            src = c_tile + c_is * kBKW;
-        }
-        auto voff = [&](int j) {
-            if constexpr (I8T) return ((j & 1) ? vp1 : vp0) + (uint32_t)(j & ~1) * ps - 1024u * (uint32_t)(j & 3);
-            else return voff_of(j);
+        // (the unpacked I8T instances have no registers for the eight hoisted piece offsets — KM = 10,
+        // L2 spilled one — so theirs are added up from the two pinned bases at every issue: nine
+        // vector adds, no division or multiply; the packed instances hoist them as the bf16 kernel does)
+        uint32_t vp[2] = {vpar[0], vpar[1]};
+        if constexpr (!PACK) asm volatile("" : "+v"(vp[0]), "+v"(vp[1]));
+        auto voff_of = [&](int j) {
+            return vp[j & 1] + (uint32_t)(j & ~1) * kPS - 1024u * (uint32_t)(j & 3);
         };
-#else
-        const uint32_t* src = c_tile + c_is * kBKW;
 #endif
+        const uint32_t* src = c_tile + c_is * kBKW;
         const uint32_t dst = smem0 + (uint32_t)((g & (kNS - 1)) * kStage) + pdst;
         if (pbase + kLPW <= c_ng || !isA) {
 #pragma unroll
             for (int h = 0; h < kLPW / 4; ++h)
-#if B16W_I8T
-                dma4x(src, dst + 4096u * h, voff(4 * h), voff(4 * h + 1), voff(4 * h + 2),
-                      voff(4 * h + 3));
-#else
                 dma4x(src, dst + 4096u * h, voff_of(4 * h), voff_of(4 * h + 1), voff_of(4 * h + 2),
                       voff_of(4 * h + 3));
-#endif
         } else {
             // the split's last, partial tile: pieces past its groups are skipped
 #pragma unroll
@@ -208,17 +171,10 @@
                 if (pbase + j < c_ng) {
                     const uint32_t d = dst + 4096u * (j / 4);
                     switch (j & 3) {
-#if B16W_I8T
-                        case 0: dma1<0>(src, d, voff(j)); break;
-                        case 1: dma1<1024>(src, d, voff(j)); break;
-                        case 2: dma1<2048>(src, d, voff(j)); break;
-                        default: dma1<3072>(src, d, voff(j)); break;
-#else
                         case 0: dma1<0>(src, d, voff_of(j)); break;
                         case 1: dma1<1024>(src, d, voff_of(j)); break;
                         case 2: dma1<2048>(src, d, voff_of(j)); break;
                         default: dma1<3072>(src, d, voff_of(j)); break;
-#endif
                     }
                 }
         }
@@ -236,9 +192,6 @@
             ++c_it;
             if (isA) {
                 c_tile = xh + (size_t)trow(c_it, 0) * dw;
-#if B16W_I8T
-                if constexpr (I8T) c_tile_t = ta.xt + (size_t)trow(c_it, 0) * ta.dwt;
-#endif
                 c_ng = c_it == t1 - 1 ? cnt - c_it * kGPT : kGPT;
             }
         }
@@ -392,7 +345,7 @@
         auto tile_stages = [&](auto nr_tag) __attribute__((always_inline)) {
             if constexpr (I8T) {
                 constexpr int NR = decltype(nr_tag)::value;
-                stage_loop(nr_tag, std::true_type{}, nst_t, 0, nst > nst_t);
+                { B16W_LOOP_BEGIN(); stage_loop(nr_tag, std::true_type{}, nst_t, 0, nst > nst_t); B16W_LOOP_END(0, nst_t); }
                 const float* scl = reinterpret_cast<const float*>(smem + kScaleOff + ((t - t0) % kNormSlots) * kBM * 4);
                 const float sq[2] = {lsq[lc], lsq[lc + 16]};
 #pragma unroll
@@ -409,7 +362,7 @@
                     // keeps every row block's scales in registers at once)
                     asm volatile("" : "+v"(acc[rb][0]), "+v"(acc[rb][1]));
                 }
-                stage_loop(nr_tag, std::false_type{}, nst - nst_t, nst_t, false);
+                { B16W_LOOP_BEGIN(); stage_loop(nr_tag, std::false_type{}, nst - nst_t, nst_t, false); B16W_LOOP_END(1, nst - nst_t); }
             } else {
                 stage_loop(nr_tag, std::false_type{}, nst, 0, false);
 #else
@@ -425,10 +378,16 @@
         else if (nlive == 2) tile_stages(std::integral_constant<int, 2>{});
         else tile_stages(std::integral_constant<int, 1>{});
 #else
+#ifdef IMGREC_B16_STAMPS
+        B16W_LOOP_BEGIN();
+#endif
         if (nlive >= 4) stage_loop(std::integral_constant<int, 4>{});
         else if (nlive == 3) stage_loop(std::integral_constant<int, 3>{});
         else if (nlive == 2) stage_loop(std::integral_constant<int, 2>{});
         else stage_loop(std::integral_constant<int, 1>{});
+#ifdef IMGREC_B16_STAMPS
+        B16W_LOOP_END(1, nst);
+#endif
 #endif
 
         // ---- top-k epilogue of tile t.  Screen: a row matters only if its key beats T = min(the
@@ -617,6 +576,13 @@
 
 #ifdef IMGREC_B16_STAMPS
     if (threadIdx.x == 0 && wg < 1024) g_b16w_wg[2 * wg + 1] = __builtin_amdgcn_s_memrealtime();
+    if (threadIdx.x == 0 && wg < 1024)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            g_b16w_loop[6 * wg + 3 * i] = lp_cyc[i];
+            g_b16w_loop[6 * wg + 3 * i + 1] = lp_rt[i];
+            g_b16w_loop[6 * wg + 3 * i + 2] = lp_n[i];
+        }
 #endif
     // ---- one list per (query, row split): fold lane quarters 2, 3 into 0, 1 (lane ^ 32), then
     // quarter 1 into 0 (lane ^ 16).  Entries a fold drops rank behind the folded list's last

@@ -76,7 +76,7 @@ int corpus_columns(knn_index* ix, Column<DeviceSpace>* cols, bool all) {
     if (all || ix->x8) cols[n++] = {&ix->x8s, (size_t)ix->nblk8 * sizeof(float)};
     if (all || ix->x8) cols[n++] = {&ix->x8r, sizeof(float)};
     // the int8 tail copy exists only once a large-batch search has materialised it (ensure_i8tail)
-    if (all || ix->xt) cols[n++] = {&ix->xt, (size_t)ix->xt_dpt};
+    if (all || ix->xt) cols[n++] = {&ix->xt, (size_t)ix->xt_row};
     if (all || ix->xt) cols[n++] = {&ix->xts, sizeof(float)};
     if (all || ix->xt) cols[n++] = {&ix->xtm, sizeof(float4)};
     return n;
@@ -155,7 +155,7 @@ int add_device_locked(knn_index* ix, const float* x, int64_t n, hipStream_t st) 
         KNN_HIP(launch_i8_rows(xb, n, ix->dp, ix->nblk8, (int8_t*)at(kColX8), (float*)at(kColX8s),
                                (float*)at(kColX8r), st));
     if (ix->xt) {
-        KNN_HIP(launch_i8tail_rows(xb, n, ix->dp, ix->dpb, ix->xt_head, ix->xt_dpt, (int8_t*)at(kColXt),
+        KNN_HIP(launch_i8tail_rows(xb, n, ix->dp, ix->dpb, ix->xt_head, ix->xt_dpt, ix->xt_row, (int8_t*)at(kColXt),
                                    (float*)at(kColXts), (float4*)at(kColXtm), st));
         ix->xt_tried = false;        // new rows can move the copy's maxima: the next search is a trial again
     }
@@ -192,8 +192,8 @@ int ensure_i8(knn_index* ix, hipStream_t st) {
     return KNN_OK;
 }
 
-// The int8 tail copy of the 256 x 256 kernel (dpt bytes + a scale + four statistics per row: 1.8 GB
-// per 1M x 1968 rows) is built on the first search that takes the route, from the stored fp32
+// The int8 tail copy of the 256 x 256 kernel (a joint row of dpt code bytes and 2 H bytes of bf16
+// head + a scale + four statistics per row: 2.2 GB per 1M x 1968 rows) is built on the first search that takes the route, from the stored fp32
 // rows, and kept up to date by later adds (the int8 scan copy's pattern).  The split column comes
 // from the corpus as it stands then (i8t_pick_head), which costs one host wait for the block
 // maxima; the decision — eligible or not — then holds until knn_reset.
@@ -212,17 +212,18 @@ int ensure_i8tail(knn_index* ix, hipStream_t st) {
     if (head < 0) { ix->xt_state = TailCopy::Ineligible; return KNN_OK; }
     ix->xt_head = head;
     ix->xt_dpt = (int)round_up(ix->dpb - head, 128);
+    ix->xt_row = i8t_joint_row_bytes(head, ix->xt_dpt);
     // no room for the copy: the index searched on the bf16 pass before and goes on doing so
-    if (materialise_columns(ix, kColXt, 3) != KNN_OK) {
+    if (ix->xt_alloc_fail || materialise_columns(ix, kColXt, 3) != KNN_OK) {
         drop_i8tail(ix, TailCopy::Ineligible);
         return KNN_OK;
     }
-    // (pad rows of the codes and scales are read by the kernel's partial tiles: zero)
-    KNN_HIP(hipMemsetAsync(ix->xt, 0, (size_t)ix->cap * ix->xt_dpt, st));
+    // (pad rows of the joint rows and scales are read by the kernel's partial tiles: zero)
+    KNN_HIP(hipMemsetAsync(ix->xt, 0, (size_t)ix->cap * ix->xt_row, st));
     KNN_HIP(hipMemsetAsync(ix->xts, 0, (size_t)ix->cap * sizeof(float), st));
     KNN_HIP(hipMemsetAsync(ix->xtm, 0, (size_t)ix->cap * sizeof(float4), st));
     ix->xn_max_stale = true;             // refresh_maxima computes the copy's maxima
-    KNN_HIP(launch_i8tail_rows(ix->xb, ix->ntotal, ix->dp, ix->dpb, head, ix->xt_dpt, ix->xt, ix->xts,
+    KNN_HIP(launch_i8tail_rows(ix->xb, ix->ntotal, ix->dp, ix->dpb, head, ix->xt_dpt, ix->xt_row, ix->xt, ix->xts,
                                ix->xtm, st));
     ix->xt_state = TailCopy::Built;
     return KNN_OK;
@@ -230,12 +231,12 @@ int ensure_i8tail(knn_index* ix, hipStream_t st) {
 
 // The copy's only teardown.  The caller has drained every stream that may still read the blocks.
 // Every caller gets the whole reset, where each used to clear its own subset of xt_head, xt_dpt and
-// xt_tried: the difference cannot be observed, since all three are read only while the copy is
+// xt_tried: the difference cannot be observed, since they (and xt_row) are read only while the copy is
 // Built (searches, adds, corpus_columns' live columns, knn_debug_i8tail) or after the next
 // ensure_i8tail wrote them on its way from Undecided.
 void drop_i8tail(knn_index* ix, TailCopy next) {
     ix->xt.reset(); ix->xts.reset(); ix->xtm.reset();
-    ix->xt_head = ix->xt_dpt = 0;
+    ix->xt_head = ix->xt_dpt = ix->xt_row = 0;
     ix->xt_tried = false; ix->xt_state = next;
 }
 
@@ -297,6 +298,8 @@ int create_single(int d, int metric, int device, knn_index** out) {
         ix->i8tail = *e != '0';
         ix->xt_no_trial = *e == '2';
     }
+    // IMGREC_I8TAIL_ALLOC_FAIL=1 (tests): the int8 tail copy's allocation fails, as on a full device
+    if (const char* e = test_knob("IMGREC_I8TAIL_ALLOC_FAIL")) ix->xt_alloc_fail = *e != '0';
     // IMGREC_RANGE_CAP=<entries> (tests): the range search's initial append capacity, so small
     // shapes reach the overflow re-run
     if (const char* e = test_knob("IMGREC_RANGE_CAP")) {
@@ -845,9 +848,32 @@ int knn_debug_i8tail(knn_index_t* ix, int* head, int* dpt, int64_t i0, int64_t n
             rc = HipStreams::fail(hipMemcpyAsync(dst, (const char*)src + (size_t)i0 * row, (size_t)n * row,
                                                  hipMemcpyDeviceToHost, ix->stream), "hipMemcpyAsync");
     };
-    down(codes, ix->xt.get(), (size_t)ix->xt_dpt);
+    // the codes are the first xt_dpt bytes of every joint row: a strided copy packs them
+    if (rc == KNN_OK && codes && n > 0)
+        rc = HipStreams::fail(hipMemcpy2DAsync(codes, (size_t)ix->xt_dpt,
+                                               (const char*)ix->xt.get() + (size_t)i0 * ix->xt_row,
+                                               (size_t)ix->xt_row, (size_t)ix->xt_dpt, (size_t)n,
+                                               hipMemcpyDeviceToHost, ix->stream), "hipMemcpy2DAsync");
     down(scales, ix->xts.get(), sizeof(float));
     down(stats, ix->xtm.get(), sizeof(float4));
+    return op.finish(rc);
+}
+
+/* Read-only view of the copy's raw joint rows for tests: *row_bytes = dpt + 2 head (a row is its dpt
+ * tail codes, then its first head columns as bf16), and rows [i0, i0 + n) of them at `rows` (n x
+ * row_bytes; NULL outputs are skipped).  KNN_EINVAL while the copy does not exist. */
+int knn_debug_i8tail_rows(knn_index_t* ix, int64_t i0, int64_t n, int* row_bytes, uint8_t* rows) {
+    if (!ix) KNN_FAIL(KNN_EINVAL, "index is NULL");
+    if (ix->multi) KNN_FAIL(KNN_EINVAL, "knn_debug_i8tail_rows: single-device indexes only");
+    IndexOp op(ix);
+    if (ix->xt_state != TailCopy::Built || !ix->xt) KNN_FAIL(KNN_EINVAL, "the index has no int8 tail copy");
+    if (i0 < 0 || n < 0 || i0 + n > ix->ntotal) KNN_FAIL(KNN_EINVAL, "rows outside [0, ntotal)");
+    if (row_bytes) *row_bytes = ix->xt_row;
+    int rc = op.begin_host();
+    if (rc == KNN_OK && rows && n > 0)
+        rc = HipStreams::fail(hipMemcpyAsync(rows, (const char*)ix->xt.get() + (size_t)i0 * ix->xt_row,
+                                             (size_t)n * ix->xt_row, hipMemcpyDeviceToHost, ix->stream),
+                              "hipMemcpyAsync");
     return op.finish(rc);
 }
 

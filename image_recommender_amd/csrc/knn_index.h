@@ -152,17 +152,20 @@ struct knn_index : imgrec::IndexShape {
     DevBuf<float> x8r;    // cap: |x - s c| per row
     DevBuf<float> x8r_max;   // device scalar, max of x8r
     // int8 tail copy of the 256 x 256 kernel (built by the first search that takes the route,
-    // ensure_i8tail; DESIGN.md "int8 tail"): columns xt_head .. dpb - 1 of every row
-    DevBuf<int8_t> xt;       // cap x xt_dpt codes, natural column order, pad 0
+    // ensure_i8tail; DESIGN.md "int8 tail"): joint rows — columns xt_head .. dpb - 1 of every row as
+    // codes, then its first xt_head columns as bf16 (the values of xh), so the kernel reads one array
+    DevBuf<int8_t> xt;       // cap x xt_row bytes: xt_dpt codes (natural column order, pad 0) | xt_head bf16
     DevBuf<float> xts;       // cap: scale max|x_tail| / 127
     DevBuf<float4> xtm;      // cap: (|x_tail - s c|, |x_head - bf16(x_head)|, |x_tail|, |x_head|), rounded up
     DevBuf<float> xt_max;    // device: the four maxima of xtm (R_t, R_h, X_t, X_h)
     int xt_head = 0, xt_dpt = 0;     // (its state: IndexShape::xt_state)
+    int xt_row = 0;                  // i8t_joint_row_bytes(xt_head, xt_dpt)
     // the copy's first search is a trial: its certificate counts decide whether the index keeps the
     // route (search_locked); false again after reset
     bool xt_tried = false;
     bool xt_no_trial = false;   // IMGREC_B16W_I8TAIL=2: no trial (measurement builds whose lists are wrong)
-    DevBuf<int8_t> qt;       // a search's query tail codes, scales and inner-product bounds
+    bool xt_alloc_fail = false; // IMGREC_I8TAIL_ALLOC_FAIL=1 (tests): the copy's allocation counts as failed
+    DevBuf<int8_t> qt;       // a search's query joint rows (nq_pad x xt_row), scales and inner-product bounds
     DevBuf<float> qts;
     DevBuf<float> q_eip;
     DevBuf<int8_t> q8;        // a search's two-level query codes

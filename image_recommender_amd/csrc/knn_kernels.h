@@ -38,12 +38,12 @@ struct TileArgs {
     // kSBWords, reset by the query prep: SharedBoundPrep); NULL = every list screens alone
     uint32_t* sbound = nullptr;
     // 256 x 256 bf16 kernel, optional: the int8 tail (knn_b16w_tile_kernel_i8t; DESIGN.md "int8
-    // tail").  xt non-NULL: columns t_head .. of every row and query come from the int8 tail copy
-    // (t_dpt codes per row, one scale per row / per query), only the first t_head columns from
-    // xb / qp
+    // tail").  xt non-NULL: the kernel reads the joint rows xt / qt (t_dpt codes of columns t_head ..,
+    // one scale per row / per query, then the first t_head columns as bf16: i8t_joint_row_bytes per
+    // row) instead of xb / qp
     const int8_t* xt = nullptr;
     const float* xts = nullptr;
-    const int8_t* qt = nullptr;     // nq_pad x t_dpt query codes
+    const int8_t* qt = nullptr;     // nq_pad joint query rows
     const float* qts = nullptr;     // nq_pad query scales
     int t_head = 0, t_dpt = 0;
 };
@@ -69,16 +69,17 @@ struct SharedBoundPrep {
 };
 
 // The int8 tail's query side, written by the same prep pass (launch_query_prep_b16) when codes is
-// set: columns head .. dpb - 1 of every query as int8 codes with one scale per query (dpt codes
-// per query, pad codes 0), and the query's inner-product error bound e_ip of the int8-tail pass
+// set: the query's joint row — columns head .. dpb - 1 as int8 codes with one scale per query (dpt
+// codes, pad codes 0), then its first head columns as bf16 (the values of its bf16 row), `row` bytes
+// in all — and the query's inner-product error bound e_ip of the int8-tail pass
 // (RerankArgs::e_ip) from the corpus maxima xt_max = (R_t, R_h, X_t, X_h).
 struct I8TailPrep {
-    int8_t* codes = nullptr;    // nq_pad x dpt; NULL = nothing to do
+    int8_t* codes = nullptr;    // nq_pad x row; NULL = nothing to do
     float* scale = nullptr;     // nq_pad
     float* e_ip = nullptr;      // nq_pad
     const float* xt_max = nullptr;
     const float* xn_max = nullptr;
-    int head = 0, dpt = 0;
+    int head = 0, dpt = 0, row = 0;
     float c_acc = 0.f;          // i8t_acc_coef(head)
 };
 
@@ -305,7 +306,7 @@ hipError_t launch_query_prep_b16(const float* src, int64_t n, int d, int dp, int
 hipError_t launch_block_absmax(const float* xb, int64_t n, int dp, int nblk, float* out, hipStream_t st);
 // rows' columns head .. dpb - 1 -> dpt int8 codes (pad 0) + scale max|x_tail| / 127 per row, and per
 // row stat = (|x_tail - s c|, |x_head - bf16(x_head)|, |x_tail|, |x_head|), each rounded up
-hipError_t launch_i8tail_rows(const float* xb, int64_t n, int dp, int dpb, int head, int dpt,
+hipError_t launch_i8tail_rows(const float* xb, int64_t n, int dp, int dpb, int head, int dpt, int row_bytes,
                               int8_t* codes, float* scale, float4* stat, hipStream_t st);
 // out[0..3] = the component-wise maxima of n rows' stat (R_t, R_h, X_t, X_h)
 hipError_t launch_i8tail_max(const float4* stat, int64_t n, float* out, hipStream_t st);

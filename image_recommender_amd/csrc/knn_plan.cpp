@@ -97,6 +97,17 @@ int i8t_pick_head(const float* blkmax, int nblk) {
     return -1;
 }
 
+// The joint row of the int8 tail copy (knn_plan.h): dpt bytes of codes, 2 head bytes of bf16.
+int i8t_joint_row_bytes(int head, int dpt) {
+    if (head < 0 || head % 64 != 0 || dpt < kI8TStageBytes || dpt % kI8TStageBytes != 0) return -1;
+    return dpt + 2 * head;
+}
+int i8t_tail_stages(int dpt) { return dpt / kI8TStageBytes; }
+int i8t_row_stages(int head, int dpt) {
+    const int rb = i8t_joint_row_bytes(head, dpt);
+    return rb < 0 ? -1 : rb / kI8TStageBytes;
+}
+
 // int8 small-batch pass (knn_i8.hip): per block an exact int32 dot of the row's and the query's
 // codes per level (exact in fp32 as well, |D| < 2^24), the fold s_x (s_hi D_hi + s_lo D_lo) into
 // the lane's accumulator (three roundings), ceil(nblk/16) blocks per lane, then the 16-lane DPP

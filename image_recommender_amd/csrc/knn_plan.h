@@ -35,6 +35,14 @@ float b16_acc_coef(int dpb);
 float i8t_acc_coef(int head);
 int i8t_pick_head(const float* blkmax, int nblk);
 constexpr int kI8TMinTail = 512;               // tail columns below which the route is off
+// The copy's joint row (and a padded query's): dpt tail codes, then the first `head` columns as
+// bf16 — one array and one stride for both operands of a tile, so the kernel stages 128 B of a row
+// per stage whichever kind the stage is.  dpt % 128 == 0 and head % 64 == 0: the row is whole
+// stages, i8t_tail_stages of codes first, then head / 64 of bf16.  (-1: not such a pair.)
+int i8t_joint_row_bytes(int head, int dpt);
+int i8t_tail_stages(int dpt);
+int i8t_row_stages(int head, int dpt);
+constexpr int kI8TStageBytes = 128;
 // int8 small-batch pass (knn_i8.hip): batches of at most kI8MaxQ queries, K' = kB16Cand
 constexpr int kI8MaxQ = 8;
 float i8_acc_coef(int nblk);

@@ -140,37 +140,42 @@ __device__ __forceinline__ void load_chunk8(const float* x, int c, int dp, float
 }
 
 // One wave per row: columns head .. dpb - 1 -> int8 codes c = rint(x / s), s = max |x_tail| / 127
-// (an all-zero tail: s = 0, codes 0), dpt codes per row with the pad 0, and the row's stat =
+// (an all-zero tail: s = 0, codes 0), dpt codes per row with the pad 0, then columns 0 .. head - 1 as
+// bf16 (RNE: the bf16 rows' values) — the joint row, row_bytes = dpt + 2 head — and the row's stat =
 // (|x_tail - s c|, |x_head - bf16(x_head)|, |x_tail|, |x_head|), each rounded up (1 + 2^-9 covers
 // the fp32 accumulation of at most dpb / 64 + 6 terms per lane).
 __global__ void __launch_bounds__(256)
 i8tail_rows_kernel(const float* __restrict__ src, int64_t n, int dp, int dpb, int head, int dpt,
-                   int8_t* __restrict__ codes, float* __restrict__ scales, float4* __restrict__ stat) {
+                   int row_bytes, int8_t* __restrict__ codes, float* __restrict__ scales, float4* __restrict__ stat) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= n) return;
     const float* x = src + row * dp;
     const int hc = head / 8;
     float amax = 0.f, nh = 0.f, nt = 0.f, rh = 0.f, rt = 0.f;
+    int8_t* oc = codes + row * row_bytes;
     for (int c = lane; c < dpb / 8; c += 64) {
         float e[8];
         load_chunk8(x, c, dp, e);
+        uint32_t hw[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
             if (c < hc) {
-                const float r = e[t] - __uint_as_float(bf16_rne(e[t]) << 16);
+                const uint32_t hb = bf16_rne(e[t]);
+                const float r = e[t] - __uint_as_float(hb << 16);
                 nh = fmaf(e[t], e[t], nh);
                 rh = fmaf(r, r, rh);
+                hw[t >> 1] |= hb << (16 * (t & 1));
             } else {
                 nt = fmaf(e[t], e[t], nt);
                 amax = fmaxf(amax, fabsf(e[t]));
             }
         }
+        if (c < hc) *reinterpret_cast<uint4*>(oc + dpt + 16 * c) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
     const float sc = amax / 127.f, inv = amax > 0.f ? 127.f / amax : 0.f;
-    int8_t* oc = codes + row * dpt;
     for (int c = hc + lane; c < hc + dpt / 8; c += 64) {
         uint32_t w[2] = {0u, 0u};
         if (c < dpb / 8) {
@@ -307,28 +312,33 @@ query_prep_b16_kernel(const float* __restrict__ src, int64_t n, int d, int dp, i
     if (tp.codes) {
         const int hc = tp.head / 8;
         float amax = 0.f, nh = 0.f, nt = 0.f, rh = 0.f;
+        // the query's joint row: dpt codes, then the head as bf16 (the values written to ob above)
+        int8_t* oc = tp.codes + row * tp.row;
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int c = lane + 64 * it;
             if (8 * c >= dpb) continue;
+            uint32_t hw[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
                 const float v = normalize ? e[it][t] * scale : e[it][t];
                 if (c < hc) {
-                    const float r = v - __uint_as_float(bf16_rne(v) << 16);
+                    const uint32_t hb = bf16_rne(v);
+                    const float r = v - __uint_as_float(hb << 16);
                     nh = fmaf(v, v, nh);
                     rh = fmaf(r, r, rh);
+                    hw[t >> 1] |= hb << (16 * (t & 1));
                 } else {
                     nt = fmaf(v, v, nt);
                     amax = fmaxf(amax, fabsf(v));
                 }
             }
+            if (c < hc) *reinterpret_cast<uint4*>(oc + tp.dpt + 16 * c) = make_uint4(hw[0], hw[1], hw[2], hw[3]);
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
         const float sc = amax / 127.f, inv = amax > 0.f ? 127.f / amax : 0.f;
         float rt = 0.f;
-        int8_t* oc = tp.codes + row * tp.dpt;
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int c = lane + 64 * it;
@@ -903,7 +913,7 @@ hipError_t launch_query_prep_b16(const float* src, int64_t n, int d, int dp, int
     if (dpb % 8 != 0 || dp % 16 != 0 || dpb < dp || dp < d) return hipErrorInvalidValue;
     if (tp && tp->codes &&
         (tp->head % 64 != 0 || tp->head < 0 || tp->head >= dpb || tp->dpt % 128 != 0 ||
-         tp->dpt < dpb - tp->head || !tp->scale || !tp->e_ip || !tp->xt_max || !tp->xn_max))
+         tp->dpt < dpb - tp->head || tp->row != tp->dpt + 2 * tp->head || !tp->scale || !tp->e_ip || !tp->xt_max || !tp->xn_max))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)((n_pad + 3) / 4)), block(256);
 #define IMGREC_QPREP(ITV) hipLaunchKernelGGL((query_prep_b16_kernel<ITV>), grid, block, 0, st, src, n, \
@@ -926,14 +936,14 @@ hipError_t launch_block_absmax(const float* xb, int64_t n, int dp, int nblk, flo
     return hipGetLastError();
 }
 
-hipError_t launch_i8tail_rows(const float* xb, int64_t n, int dp, int dpb, int head, int dpt,
+hipError_t launch_i8tail_rows(const float* xb, int64_t n, int dp, int dpb, int head, int dpt, int row_bytes,
                               int8_t* codes, float* scale, float4* stat, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     if (dpb % 64 != 0 || dp % 8 != 0 || dpb < dp || head % 64 != 0 || head < 0 || head >= dpb ||
-        dpt % 128 != 0 || dpt < dpb - head)
+        dpt % 128 != 0 || dpt < dpb - head || row_bytes != dpt + 2 * head)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(i8tail_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, xb, n, dp, dpb,
-                       head, dpt, codes, scale, stat);
+                       head, dpt, row_bytes, codes, scale, stat);
     return hipGetLastError();
 }
 

@@ -329,12 +329,12 @@ int i8tail_prep(knn_index* ix, const RoutePlan& rp, hipStream_t st, I8TailPrep* 
     int rc;
     if ((rc = ensure_i8tail(ix, st)) != KNN_OK || ix->xt_state != TailCopy::Built) return rc;
     if ((rc = refresh_maxima(ix, st)) != KNN_OK) return rc;
-    if ((rc = ix->qt.reserve((size_t)p.nq_pad * ix->xt_dpt)) != KNN_OK) return rc;
+    if ((rc = ix->qt.reserve((size_t)p.nq_pad * ix->xt_row)) != KNN_OK) return rc;
     if ((rc = ix->qts.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
     if ((rc = ix->q_eip.reserve((size_t)p.nq_pad)) != KNN_OK) return rc;
     tp->codes = ix->qt; tp->scale = ix->qts; tp->e_ip = ix->q_eip;
     tp->xt_max = ix->xt_max; tp->xn_max = ix->xn_max;
-    tp->head = ix->xt_head; tp->dpt = ix->xt_dpt;
+    tp->head = ix->xt_head; tp->dpt = ix->xt_dpt; tp->row = ix->xt_row;
     tp->c_acc = i8t_acc_coef(ix->xt_head);
     return KNN_OK;
 }

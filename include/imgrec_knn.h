@@ -342,6 +342,11 @@ int knn_plan_kernel(const knn_index_t* index, int64_t nq, int k, char* name, int
  * not exist (no search has taken the route yet, or the index is not eligible). */
 int knn_debug_i8tail(knn_index_t* index, int* head, int* dpt, int64_t i0, int64_t n, int8_t* codes,
                      float* scales, float* stats);
+/* The same copy's raw rows, read-only, for tests (NULL outputs are skipped).  The copy stores one
+ * joint row per corpus row: its dpt tail codes, then its first `head` columns as bf16 (the values of
+ * the bf16 rows), *row_bytes = dpt + 2 head bytes in all; rows [i0, i0 + n) of them go to `rows`
+ * (n x row_bytes).  KNN_EINVAL while the copy does not exist. */
+int knn_debug_i8tail_rows(knn_index_t* index, int64_t i0, int64_t n, int* row_bytes, uint8_t* rows);
 
 const char* knn_last_error(void);
 const char* knn_version(void);

@@ -35,6 +35,7 @@ VLADENC_CHUNK_ROWS = 128
 VLADENC_SUPER_ROWS = 2048
 VLADTRAIN_MAX_BATCH = 4096    # include/imgrec_vladtrain.h
 VLADTRAIN_MAX_BATCH_FLOATS = 1 << 28
+RESIZE_U8_HWC, RESIZE_F32_CHW = 0, 1    # include/imgrec_resize.h
 VLADTRAIN_PARAMS, VLADTRAIN_ADAM_M, VLADTRAIN_ADAM_V, VLADTRAIN_GRADS = 0, 1, 2, 3
 
 
@@ -158,6 +159,10 @@ SIGNATURES = {
     "vit_linear_bf16_split": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "vit_linear_splits": (_i, [_i64, _i]),
     "color_hist_batch_async": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
+    # imgrec_resize.h
+    "resize_lanczos_host": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
+    "resize_lanczos_device": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    "resize_last_error": (C.c_char_p, []),
     # imgrec_ingest.h
     "ingest_parse_f32": (_i64, [_vp, _i64, _vp, _i64]),
     "ingest_concat_rows": (_i64, [C.POINTER(_vp), _pi64, _i64, _i, _pi64, _vp, _vp]),

@@ -10,6 +10,7 @@ signatures):
 * ``csrc/vladenc.hip`` — the SIFT-VLAD MLP encoder's forward pass (include/imgrec_vladenc.h)
 * ``csrc/vladtrain.hip`` — the encoder's training step: losses, backward, Adam (include/imgrec_vladtrain.h)
 * ``csrc/color_hist.hip`` — the per-image colour histogram (include/imgrec_color.h)
+* ``csrc/resize.hip`` — Pillow's 8-bit LANCZOS resize of a ragged batch (include/imgrec_resize.h)
 * ``csrc/ingest.cpp`` — the SQLite pickle-BLOB fast path (include/imgrec_ingest.h)
 
 The library is built in-tree so that it travels to the GPU box with the repository snapshot.
@@ -36,12 +37,12 @@ ARCH = os.environ.get("IMGREC_OFFLOAD_ARCH", "gfx950")
 SOURCES = ["knn_kernels.hip", "knn_b16w.hip", "knn_refine.hip", "knn_capi.cpp", "knn_plan.cpp",
            "knn_search.cpp", "knn_multi.cpp", "knn_io.cpp", "ivfpq_capi.cpp", "color_hist.hip",
            "ingest.cpp", "ivfpq.hip", "knn_largek.hip", "knn_hugek.hip", "vit_fused.hip", "vit_attn.hip", "knn_i8.hip", "vit_gemm.hip",
-           "knn_range.hip", "knn_filter.hip", "knn_remove.hip", "knn_kmeans.hip", "vlad.hip", "vladenc.hip", "vladtrain.hip"]
+           "knn_range.hip", "knn_filter.hip", "knn_remove.hip", "knn_kmeans.hip", "vlad.hip", "vladenc.hip", "vladtrain.hip", "resize.hip"]
 HEADERS = ["knn_kernels.h", "knn_consts.h", "knn_plan.h", "knn_index.h", "dev_buf.h", "knn_multi.h", "wave_ops.h", "knn_certify.h", "lds_dma.h", "knn_b16w_body.inc", "knn_tile.h", "rows_geom.h", "rows_tile.h", "dev_workspace.h", "stream_fence.h", "../../include/imgrec_ivfpq.h",
            "../../include/imgrec_knn.h", "../../include/imgrec_color.h", "../../include/imgrec_ingest.h",
            "../../include/imgrec_vit.h", "../../include/imgrec_kmeans.h", "vlad_args.h",
            "../../include/imgrec_vlad.h", "vladenc_args.h", "../../include/imgrec_vladenc.h", "vladenc_kernels.h",
-           "vladtrain_args.h", "../../include/imgrec_vladtrain.h"]
+           "vladtrain_args.h", "../../include/imgrec_vladtrain.h", "../../include/imgrec_resize.h"]
 
 
 def _hipcc() -> str:

@@ -449,10 +449,13 @@ class DreamSimVectorIndexer(BaseVectorIndexer):
     def __init__(self, db_path: str, base_dir: str, batch_size: int = 4096, model_batch: int = 128,
                  log_file: str = "dreamsim_indexer.log", log_dir: str = "logs",
                  weights_path: str | None = None, allow_random_init: bool = False,
-                 device: str | None = None):
+                 device: str | None = None, device_resize: bool = False):
         super().__init__(db_path, base_dir, batch_size, log_file, log_dir)
         torch, _, _ = _torch()
         self.model_batch = model_batch
+        # resize on the GPU (image_recommender_amd.resize: Pillow's LANCZOS bit for bit) instead of
+        # per image on the host; takes effect when the model is on the GPU
+        self.device_resize = device_resize
         self.device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
         self._log_and_print(f"Using device: {self.device}", level="info")
         self._setup_model(weights_path, allow_random_init)
@@ -485,8 +488,30 @@ class DreamSimVectorIndexer(BaseVectorIndexer):
             emb = self.model.embed(images)
         return F.normalize(emb.float(), dim=-1)
 
+    def _batch_image_to_vector_device(self, image_paths):
+        """The chunk decoded at full size, packed, uploaded once and resized to 224 x 224 on the
+        device: the tensor the default path builds (float32 CHW in [0, 1]), bit for bit."""
+        torch, _, _ = _torch()
+        from ..resize import lanczos_resize_device, pack_images
+        images, valid = [], []
+        for rel in image_paths:
+            arr = load_image(self.base_dir / rel, img_size=None, normalize=False, as_array=True)
+            if arr is None:
+                self._log_and_print(f"Error loading {self.base_dir / rel}", level="warning")
+                continue
+            images.append(arr)
+            valid.append(rel)
+        if not images:
+            return torch.empty(0, self.dim), []
+        buf, offsets, shapes, _ = pack_images(images)
+        pixels = torch.from_numpy(buf).to(self.device)
+        batch = lanczos_resize_device(pixels, offsets, shapes, (224, 224), "f32")
+        return self.embed_tensor(batch).cpu(), valid
+
     def _batch_image_to_vector(self, image_paths):
         torch, _, _ = _torch()
+        if self.device_resize and self.device.type == "cuda":
+            return self._batch_image_to_vector_device(image_paths)
         images, valid = [], []
         for rel in image_paths:
             arr = load_image(self.base_dir / rel, img_size=(224, 224), normalize=True, as_array=True)

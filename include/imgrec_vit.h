@@ -20,25 +20,35 @@ extern "C" {
 
 /* Per row r of `rows` (row length dim <= 1024): x[r] += delta[r] (bf16, when delta != NULL;
  * x is updated in place), then y[r] = bf16(LayerNorm(x[r]) * gamma + beta) with the biased
- * variance and `eps` (torch.nn.LayerNorm semantics, fp32 arithmetic). */
+ * variance and `eps` (torch.nn.LayerNorm semantics, fp32 arithmetic).  With delta == NULL x is not
+ * written.  Pointers of any alignment are accepted; the vector path (16-B fp32 and 8-B bf16
+ * accesses) is taken only when x, gamma and beta are 16-B aligned, delta and y are 8-B aligned and
+ * dim % 256 == 0, and every other call takes the lane-strided kernel: same result up to the order
+ * of the row sums.  -1 for rows < 0, dim < 1, dim > 1024 or a NULL x, gamma, beta or y; rows == 0
+ * is 0 and launches nothing. */
 int vit_add_layernorm_bf16(float* x, const uint16_t* delta, const float* gamma, const float* beta,
                            uint16_t* y, int64_t rows, int dim, float eps, void* stream);
 
-/* In place on n bf16 values: h = bf16(h * sigmoid(1.702 h)) (CLIP's QuickGELU), fp32 inside. */
+/* In place on n bf16 values: h = bf16(h * sigmoid(1.702 h)) (CLIP's QuickGELU), fp32 inside.
+ * h must be 16-B aligned: -1 otherwise, as for n < 0 or a NULL h with n > 0; n == 0 is 0. */
 int vit_quick_gelu_bf16(uint16_t* h, int64_t n, void* stream);
 
 /* In place on n bf16 values: h = bf16(0.5 h (1 + erf(h / sqrt 2))) (nn.GELU, the DINO and
- * OpenCLIP towers' MLP activation), fp32 inside. */
+ * OpenCLIP towers' MLP activation), fp32 inside.  h must be 16-B aligned: -1 otherwise, as for
+ * n < 0 or a NULL h with n > 0; n == 0 is 0. */
 int vit_gelu_bf16(uint16_t* h, int64_t n, void* stream);
 
 /* The tower input as GEMM rows: image (batch, 3, height, width) fp32 -> bf16(((x - mean[c]) /
  * std[c])) patches (batch, (height/patch)(width/patch), 3 patch patch), each laid out (c, kh, kw)
- * like the stride-`patch` patch conv's weight (patch a multiple of 8; 16-B aligned pointers). */
+ * like the stride-`patch` patch conv's weight (patch a positive multiple of 8 that divides height
+ * and width; img and out 16-B aligned; anything else, or a NULL pointer, is -1; batch == 0 is 0). */
 int vit_patchify_bf16(const float* img, int64_t batch, int height, int width, int patch,
                       const float* mean, const float* std_, uint16_t* out, void* stream);
 
 /* Token rows: out (batch, npatch + 1, dim) fp32 = [cls + pos[0] ; fp32(patch_emb[b]) + pos[1:]]
- * (patch_emb bf16 (batch, npatch, dim); dim a multiple of 4; 16-B aligned fp32 pointers). */
+ * (patch_emb bf16 (batch, npatch, dim), 8-B aligned and not NULL even when npatch == 0; dim a
+ * positive multiple of 4; npatch >= 0; 16-B aligned fp32 pointers; anything else is -1;
+ * batch == 0 is 0). */
 int vit_tokens_f32(const uint16_t* patch_emb, const float* cls, const float* pos, int64_t batch,
                    int npatch, int dim, float* out, void* stream);
 
